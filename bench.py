@@ -9,8 +9,11 @@
 Headline = BASELINE.json's metric, "images/sec fwd+bwd at 608^2": one "step" = one TRAINING step of Darknet-53 (forward with
 batch-stat BatchNorm + the reference's loss + backward + gradient all-reduce + SGD-nesterov) on the hand-written HIP
 TrainEngine -- configs[3] at N=1 (bs 64), configs[4] at N>1 (32 images per GPU, RCCL all-reduce of the 250 MB gradient);
-W warm-up steps, exactly K timed steps between barriers, max over ranks.  Rank 0 prints ONE JSON line.  Besides the contract
-keys it carries
+W warm-up steps, exactly K timed steps between barriers, max over ranks.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, the W warm-up steps, the K timed steps, the outputs of the last timed step
+(--dump-outputs DIR), the line.  Its "roofline" is the whole step's (3 x forward FLOP / step time).  Everything below is measured
+with --full only; the same line then carries, besides the contract keys,
   "roofline"      the dominant MFMA kernel OF THE TRAIN STEP, measured in this run: after the timed region the engine launches two
                   steps eagerly with HIP events around every library call on the launch stream ("train_step_kernels" is the whole
                   table); algorithmic FLOP of the kernel's calls / their summed duration vs the bf16 dense MFMA peak; "traffic" =
@@ -24,6 +27,14 @@ keys it carries
   "nms"           BASELINE configs[2]: rotated IoU + NMS on 50 000 boxes (box-pairs/s) with its VALU roofline
   "cpu_baseline"  N=1 only: the same training step (ATen fp32 chain + loss mirror + autograd) on the host cores at bs 2
   "plumbing"      BASELINE configs[0]: yolov3-tiny, 4x608^2, CPU forward + CPU rotated NMS (no GPU)
+  "allreduce"     N>1 only: the collectives alone and the step without them (with "single_rank_same_bs")
+  "train_step_hbb" the same step with the reference's hbb loss
+
+--dump-outputs DIR writes what the last timed train step computed, as DIR/<name>.npy (float32): "loss" and "loss_items" (what the
+step returns), "head0".."head2" (the raw head tensors of its forward) and "model_state" (every floating-point entry of the state
+dict after the SGD step, in state-dict order).  An array of more than 2 M elements is a fixed sample: the sorted indices of
+torch.randint(0, numel, (2 M,)) from a generator seeded with 0, the same for every run of the same arguments.  Inputs and weights
+are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -124,7 +135,15 @@ def main():
     ap.add_argument("--rank-timeout", type=float, default=1500.0,
                     help="N > 1: seconds after which rank 0 prints a failure line (which rank was in which phase) instead of waiting forever "
                          "on a collective a dead rank never joins")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs (forward, detect, NMS, hbb step, CPU baselines, kernel tables, collectives alone, "
+                         "build identity); a plain run times the headline train step only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed train step computed to DIR/<name>.npy (float32, sampled "
+                         "above 2 M elements per array)")
     args = ap.parse_args()
+    if not args.full and args.mode == "forward" and (args.no_train or args.dump_ops or args.graph or args.fwd_steps):
+        ap.error("--no-train, --dump-ops, --graph and --fwd-steps concern the forward leg, which only --full runs")
     if args.no_graph:
         os.environ["RYOLO_NO_GRAPH"] = "1"
     # stdout carries exactly ONE line (the JSON): libraries that write to fd 1 (RCCL prints a version banner from C
@@ -248,7 +267,17 @@ def _bench_body(args, world, rank, dev):
     import torch.distributed as dist
     _phase(args, "start")
     if args.mode == "train":
-        return bench_train(args, world, rank, dev)
+        return bench_train(args, world, rank, dev, dump=args.dump_outputs)
+    if not args.full:
+        # the headline alone: configs[3] (N=1) / configs[4] (N>1) with the riou loss, as the --full line reports it
+        res = bench_train(args, world, rank, dev, embedded=True, steps=args.train_steps or args.steps, warmup=args.warmup,
+                          bs=args.train_bs or (64 if world == 1 else 32), riou=True, dump=args.dump_outputs)
+        if rank == 0:
+            emit_json(res)
+        if args.use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     from rotate_yolov3_amd.cfg import make_cfg
     from rotate_yolov3_amd.model.engine import HipEngine
     from rotate_yolov3_amd.model.models import Darknet
@@ -356,7 +385,8 @@ def _bench_body(args, world, rank, dev):
             # configs[3] is quoted at bs=64 on one GPU, configs[4] at 32 per GPU
             # headline = BASELINE configs[3] as written: "full train.py step with riou loss"
             train_res = bench_train(args, world, rank, dev, embedded=True, steps=args.train_steps or args.steps,
-                                    warmup=args.warmup, bs=args.train_bs or (64 if world == 1 else 32), riou=True)
+                                    warmup=args.warmup, bs=args.train_bs or (64 if world == 1 else 32), riou=True,
+                                    dump=args.dump_outputs)
         except Exception as e:      # never lose the headline line to the secondary measurement
             if world > 1:           # ... but a rank that failed must SAY so: its peers are inside collectives it will never join (main()'s handler
                 raise               # publishes the failure through the rank monitor; rank 0 then prints the failure line)
@@ -626,11 +656,12 @@ def load_train_kernel_table():
         return None
 
 
-def bench_train(args, world, rank, dev, embedded=False, steps=None, warmup=None, bs=None, riou=False):
+def bench_train(args, world, rank, dev, embedded=False, steps=None, warmup=None, bs=None, riou=False, dump=""):
     """configs[3] (N=1) / configs[4] (N>1): one optimisation step per "step": forward (batch-stat BatchNorm) + the
     reference's hbb loss mirror + backward + gradient all-reduce (rotate-yolov3_amd/dist.py over RCCL) + SGD-nesterov.
     --train-backend hip: the hand-written TrainEngine (conv fwd/dgrad/wgrad on MFMA, BN+PReLU fwd/bwd kernels);
-    --train-backend torch: the ATen chain under bf16 autocast (MIOpen), kept as the library yardstick."""
+    --train-backend torch: the ATen chain under bf16 autocast (MIOpen), kept as the library yardstick.
+    dump: directory for the outputs of the last timed step (rank 0; see the module docstring)."""
     import torch
     import torch.distributed as dist
     from rotate_yolov3_amd.cfg import make_cfg
@@ -659,6 +690,7 @@ def bench_train(args, world, rank, dev, embedded=False, steps=None, warmup=None,
     tg = synthetic_targets(bs, seed=1 + rank, device=dev)
 
     marks = []
+    last = {}
 
     def mark():
         if args.breakdown:
@@ -672,6 +704,8 @@ def bench_train(args, world, rank, dev, embedded=False, steps=None, warmup=None,
             pred = model(x)
         mark()
         loss, items = compute_loss([p.float() for p in pred], tg.clone(), model, hyp)
+        if dump:
+            last["pred"], last["loss"] = pred, loss
         mark()
         loss.backward()
         mark()
@@ -699,6 +733,8 @@ def bench_train(args, world, rank, dev, embedded=False, steps=None, warmup=None,
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
     elapsed_local = elapsed
+    if dump and rank == 0:          # before anything below steps the model again
+        dump_outputs(dump, last["loss"], items, last["pred"], model)
     if args.breakdown and rank == 0:
         m = marks[-5 * nsteps:]
         names = ["forward", "loss", "backward", "allreduce+optimizer"]
@@ -713,7 +749,7 @@ def bench_train(args, world, rank, dev, embedded=False, steps=None, warmup=None,
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     comm = None
-    if args.use_dist and riou:
+    if args.use_dist and riou and args.full:
         # the collective on its own (nothing to hide under) and what the step shows of it: the same steps without the
         # collectives (gradient-accumulation mode of the reducer), max over ranks
         _phase(args, "train leg: collectives alone / step without collectives")
@@ -749,7 +785,7 @@ def bench_train(args, world, rank, dev, embedded=False, steps=None, warmup=None,
         every_fb = gather_floats([1.0 if (eng_me and eng_me[0].graph_fallback) else 0.0], world, dev, args.dist_backend)
         fallback_ranks = [r for r, v in enumerate(every_fb) if float(v[0]) > 0 and r != 0]
     table, step_roof = (None, None)
-    if rank == 0 and (riou or not embedded) and not args.use_dist and args.train_backend == "hip" and not args.no_kernel_table:
+    if rank == 0 and ((riou and args.full) or not embedded) and not args.use_dist and args.train_backend == "hip" and not args.no_kernel_table:
         try:
             table, step_roof = traced_train_table(model, step, dev, dump_calls=args.dump_train_calls)
         except Exception as e:      # noqa: BLE001  the table is a secondary measurement
@@ -805,6 +841,29 @@ def bench_train(args, world, rank, dev, embedded=False, steps=None, warmup=None,
         dist.barrier()
         dist.destroy_process_group()
     return res
+
+
+DUMP_SAMPLE = 2 << 20       # elements kept of a larger output array
+
+
+def dump_outputs(path, loss, items, pred, model):
+    """--dump-outputs: what the last timed train step computed, as float32 .npy files (module docstring)"""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, t):
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+    save("loss", loss)
+    save("loss_items", items)
+    for i, p in enumerate(pred):
+        save("head%d" % i, p)
+    save("model_state", torch.cat([v.detach().float().reshape(-1) for v in model.state_dict().values() if v.dtype.is_floating_point]))
 
 
 def cpu_baseline_forward(cfg, sd, size):

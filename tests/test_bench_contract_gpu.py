@@ -1,5 +1,5 @@
-"""GPU tier: bench.py's output contract -- exactly one JSON line on stdout with the driver's keys, the roofline and
-cpu_baseline objects, and the secondary measurements; run small (bs 2, 160x160) so it takes seconds."""
+"""GPU tier: bench.py's output contract -- exactly one JSON line on stdout with the driver's keys; with --full also the roofline
+and cpu_baseline objects and the secondary measurements; run small (bs 2, 160x160) so it takes seconds."""
 import json
 import os
 import subprocess
@@ -12,8 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_json_line_with_the_contract_keys(cuda_dev):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--bs", "2", "--size", "160",
-                        "--train-bs", "2"], cwd=ROOT, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--bs", "2",
+                        "--size", "160", "--train-bs", "2"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.split("\n") if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -54,13 +54,50 @@ def test_bench_prints_one_json_line_with_the_contract_keys(cuda_dev):
     assert d["build"]["library_is_this_tree"] is True and len(d["build"]["library_id"]) == 16
 
 
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_outputs(cuda_dev, tmp_path):
+    """A plain run: the headline train step alone (no secondary legs), exactly --steps timed steps, and with --dump-outputs the
+    arrays of its last step as float32 .npy files -- identical inputs from run to run."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "2", "--size", "160", "--train-bs", "2"]
+    r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / "a")], cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.split("\n") if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "roofline", "loss_items"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 2 and d["unit"] == "images/s" and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert "fwd+bwd" in d["metric"] and "configs[3]" in d["config"]["workload"] and "riou loss" in d["config"]["workload"]
+    assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) <= 0.02 * d["value"]
+    for k in ("forward", "cpu_baseline", "plumbing", "nms", "detect", "train_step_hbb", "train_step_kernels", "build"):
+        assert k not in d, k
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == ["head0.npy", "head1.npy", "head2.npy", "loss.npy", "loss_items.npy", "model_state.npy"], names
+    total = 0
+    for n in names:
+        a = np.load(str(tmp_path / "a" / n))
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.allclose(np.load(str(tmp_path / "a" / "loss_items.npy")), d["loss_items"], rtol=1e-3, atol=1e-4)
+    # a second run of the same arguments: the same inputs, so the same outputs up to the order of floating-point atomics
+    r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / "b")], cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    for n in names:
+        a, b = np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n))
+        assert a.shape == b.shape, n
+        scale = max(float(np.abs(a).mean()), 1e-12)
+        assert float(np.abs(a - b).mean()) <= 1e-3 * scale and float(np.abs(a - b).max()) <= 0.05 * float(np.abs(a).max()) + 1e-12, n
+
+
 def test_bench_gpus_2_launches_itself_as_two_ranks(cuda_dev):
     """`python bench.py --gpus 2` as the driver invokes it (no torchrun wrapper, no WORLD_SIZE): the script re-executes itself
     under torch.distributed.run with two ranks.  On this one-GPU box both ranks share cuda:0 and the process group is gloo
     (RCCL refuses two ranks on one device); on the 8-GPU node the same path runs one rank per GPU over RCCL."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--dist-backend", "gloo",
-                        "--steps", "2", "--warmup", "1", "--bs", "2", "--size", "160", "--train-bs", "2", "--no-nms"],
+                        "--full", "--steps", "2", "--warmup", "1", "--bs", "2", "--size", "160", "--train-bs", "2", "--no-nms"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.split("\n") if ln.strip().startswith("{")]

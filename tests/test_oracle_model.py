@@ -175,15 +175,6 @@ def test_product_parser_reproduces_the_reference_parser_on_every_loadable_refere
             raw5 = [" /py/rotated-yolo/" + r.strip() if "txt" in r else r for r in v["anchors_raw"]]
             cfg.write_text(_serialise(v["blocks"], raw5))
             _same_defs(parse_model_cfg(str(cfg)), v["blocks"], arrays)
-    # the reference's own files, where they exist (build container only)
-    if os.path.isdir("/root/reference"):
-        cwd = os.getcwd()
-        os.chdir("/root/reference")
-        try:
-            for path, v in loadable.items():
-                _same_defs(parse_model_cfg(path), v["blocks"], arrays)
-        finally:
-            os.chdir(cwd)
 
 
 def test_product_hyp_parse_equals_the_reference_on_every_shipped_hyp_file(tmp_path):
@@ -198,10 +189,6 @@ def test_product_hyp_parse_equals_the_reference_on_every_shipped_hyp_file(tmp_pa
         assert set(got) == set(v["parsed"])
         for k, want in v["parsed"].items():
             assert float(got[k]) == want, (path, k, got[k], want)
-    if os.path.isdir("/root/reference"):
-        for path, v in fx["hyps"].items():
-            got = hyp_parse(os.path.join("/root/reference", path))
-            assert {k: float(x) for k, x in got.items()} == v["parsed"]
 
 
 def test_product_loads_weights_and_checkpoint_written_by_the_reference(tmp_path):

@@ -1,0 +1,611 @@
+"""Dispatch census: every convolution launch the engines make over the accepted input space, and the kernel the library's
+shape-driven dispatch picks for it.  A helper module of the suite (not a conftest): tests/test_dispatch_census.py (CPU tier) and
+tests/test_dispatch_coverage_gpu.py (GPU tier) import it.
+
+The engines build their per-block descriptors while they allocate their activation buffers (model/engine.py HipEngine.__init__,
+model/train_engine.py TrainEngine.__init__), so the planning rules are mirrored here on buffer stand-ins (`_V`: channel stride,
+channel offset, identity) instead of tensors.  test_dispatch_coverage_gpu.py::test_census_matches_the_engines pins this mirror to
+the engines field by field.
+
+Call forms recorded per block:
+  eval      ryolo_conv_kernel_choice(d, residual, 0) of the inference engine's single-conv launches
+  pair      ryolo_conv_pair_supported: the fused stem pair of the inference engine (conv_stem.hip)
+  head      ryolo_conv_head_decode_supported: a YOLO head conv + decode in one launch (conv_pw.hip)
+  train     ryolo_conv_kernel_choice(d, 0, statistics) of the training forward (+ ryolo_conv0_recompute_supported)
+  dgrad     ryolo_conv_dgrad_kernel_choice(d, with_bn_reduce), the flag as TrainEngine._plan_reduce_fusion sets it
+  wgrad     ryolo_conv_wgrad_kernel_choice(d) and the split-K count (from ryolo_conv_wgrad_workspace_bytes)
+
+Edge class = (form, kernel code, ksize, stride, edge bits); the bits are derived per kernel family from its launch code (each
+helper below cites the lines it mirrors).  The device's CU count enters the persistent-grid bits: pass the real one on a GPU.
+"""
+import ctypes as C
+
+import rotate_yolov3_amd  # noqa: F401  (installs the package under its importable name)
+from rotate_yolov3_amd import _lib
+from rotate_yolov3_amd.cfg import make_cfg
+from rotate_yolov3_amd.model import engine as _engine  # noqa: F401  (declares ryolo_conv_head_decode_supported)
+from rotate_yolov3_amd.model import hip_ops as ops
+from rotate_yolov3_amd.model import hip_train_ops as tr
+from rotate_yolov3_amd.utils.parse_config import parse_model_cfg_text, yolo_mask
+
+CONFIGS = (("darknet53", 1), ("darknet53", 2), ("darknet53", 15), ("tiny", 1), ("tiny", 80))
+SQUARE = tuple((s, s) for s in range(320, 609, 32))
+RECT = ((416, 640), (608, 352), (512, 384))          # (height, width)
+SIZES = SQUARE + RECT
+BATCHES = (1, 2, 4, 8, 16, 32, 64)
+
+BK = 64          # conv_common.h:21 K elements per step
+KP = 64          # train.hip:76 pixels per weight-gradient K step
+WGRAD_TAPS = 1000
+
+DESC_FIELDS = [f for f, _ in ops.ConvDesc._fields_]
+
+
+def desc_tuple(d):
+    return tuple(round(getattr(d, f), 6) if f == "slope" else getattr(d, f) for f in DESC_FIELDS)
+
+
+def mk_desc(t):
+    return ops.ConvDesc(*t)
+
+
+class Refused(RuntimeError):
+    """the engine refuses this configuration (HipEngine raises RuntimeError at plan time)"""
+
+
+class _V(object):
+    """a buffer view: `base` identifies the allocation, `off` the channel offset inside it, `cs` the pixel stride"""
+    __slots__ = ("base", "off", "cs", "C", "H", "W")
+
+    def __init__(self, C_, H, W, base=None, off=0, cs=None):
+        self.base = base if base is not None else object()
+        self.off, self.C, self.H, self.W = off, C_, H, W
+        self.cs = cs if cs is not None else C_
+
+    def ptr(self):
+        return (id(self.base), self.off)
+
+
+def _abs(i, l):
+    return l if l > 0 else i + l
+
+
+def config_defs(kind, nc, H, W):
+    text = make_cfg.darknet53(W, H, classes=nc) if kind == "darknet53" else make_cfg.tiny(W, H, classes=nc)
+    defs = parse_model_cfg_text(text)
+    assert defs[0]["type"] == "net"
+    return defs[1:]
+
+
+def _conv(d):
+    k = int(d["size"])
+    act = d.get("activation", "linear")
+    return dict(cout=int(d["filters"]), k=k, s=int(d["stride"]), pad=(k - 1) // 2 if int(d.get("pad", 0)) else 0,
+                bn=int(d["batch_normalize"]) != 0, act=ops.ACT_LEAKY if act == "leaky" else (ops.ACT_MISH if act == "mish" else ops.ACT_LINEAR),
+                slope=0.1 if act == "leaky" else 0.0)
+
+
+def _shapes(defs, H, W, train):
+    shp = []
+    c, h, w = 3, H, W
+    for i, d in enumerate(defs):
+        t = d["type"]
+        if t == "convolutional":
+            cv = _conv(d)
+            c, h, w = cv["cout"], (h + 2 * cv["pad"] - cv["k"]) // cv["s"] + 1, (w + 2 * cv["pad"] - cv["k"]) // cv["s"] + 1
+        elif t == "maxpool":
+            if train:
+                raise ValueError("maxpool graphs do not train")
+            k, s = int(d["size"]), int(d["stride"])
+            if not (k == 2 and s == 1):
+                p = (k - 1) // 2
+                h, w = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
+        elif t == "upsample":
+            h, w = h * int(d["stride"]), w * int(d["stride"])
+        elif t == "route":
+            ls = [_abs(i, int(v)) for v in d["layers"].split(",")]
+            c = sum(shp[l][0] for l in ls)
+            h, w = shp[ls[0]][1], shp[ls[0]][2]
+        shp.append((c, h, w))
+    return shp
+
+
+def _readers(defs):
+    readers = [[] for _ in defs]
+    for i, d in enumerate(defs):
+        if d["type"] == "route":
+            for v in d["layers"].split(","):
+                readers[_abs(i, int(v))].append(i)
+        else:
+            if i > 0:
+                readers[i - 1].append(i)
+            if d["type"] == "shortcut":
+                readers[_abs(i, int(d["from"]))].append(i)
+    return readers
+
+
+def _L():
+    return _lib.lib()
+
+
+def _choice(t, residual, stats):
+    return _L().ryolo_conv_kernel_choice(C.byref(mk_desc(t)), 1 if residual else 0, 1 if stats else 0)
+
+
+# ------------------------------------------------------------------------------------------------ eval engine mirror
+def eval_blocks(defs, H, W, N):
+    """model/engine.py HipEngine.__init__ steps 1-4, conv launches only: [dict(form, layer, name, desc(s), ...)]"""
+    n = len(defs)
+    shp = _shapes(defs, H, W, False)
+    readers = _readers(defs)
+    fused_into, conv_res, conv_ups = {}, {}, {}
+    for i, d in enumerate(defs):
+        if i == 0 or defs[i - 1]["type"] != "convolutional" or readers[i - 1] != [i] or (i - 1) in fused_into.values():
+            continue
+        if d["type"] == "shortcut" and _abs(i, int(d["from"])) != i - 1:
+            fused_into[i] = i - 1
+            conv_res[i - 1] = _abs(i, int(d["from"]))
+        elif d["type"] == "upsample" and int(d["stride"]) == 2:
+            fused_into[i] = i - 1
+            conv_ups[i - 1] = 2
+    views, home, alias = [None] * n, {}, {}
+    for i, d in enumerate(defs):
+        if d["type"] != "route":
+            continue
+        ls = [_abs(i, int(v)) for v in d["layers"].split(",")]
+        if len(ls) == 1:
+            alias[i] = ls[0]
+            continue
+        c, h, w = shp[i]
+        buf = _V(c, h, w)
+        views[i] = buf
+        off = 0
+        for l in ls:
+            src = l
+            while src in alias:
+                src = alias[src]
+            if src not in home and defs[src]["type"] in ("convolutional", "shortcut", "upsample", "maxpool") and src < i \
+                    and shp[src][0] % 8 == 0 and off % 8 == 0:
+                home[src] = _V(shp[src][0], h, w, base=buf.base, off=off, cs=c)
+            off += shp[l][0]
+
+    def view_for(i):
+        return home[i] if i in home else _V(*shp[i])
+
+    x_nhwc = _V(8, H, W)
+    out_recs = []
+    pending = None
+    pending_head = None
+    for i, d in enumerate(defs):
+        t = d["type"]
+        if i in fused_into:
+            views[i] = views[fused_into[i]]
+            continue
+        if t == "convolutional":
+            cv = _conv(d)
+            xin = x_nhwc if i == 0 else views[i - 1]
+            cin_k = pending["cout"] if pending is not None else xin.C
+            final, res, ups = i, None, 1
+            if i in conv_res:
+                res, final = views[conv_res[i]], i + 1
+            if i in conv_ups:
+                ups, final = 2, i + 1
+            pair_first = pending is None and i + 1 < n and defs[i + 1]["type"] == "convolutional" and readers[i] == [i + 1] and \
+                i not in conv_res and i not in conv_ups and i not in home and (i + 1) not in conv_ups
+            head_cand = (not cv["bn"] and cv["k"] == 1 and cv["s"] == 1 and i + 1 < n and defs[i + 1]["type"] == "yolo" and
+                         readers[i] == [i + 1] and i not in home and i not in conv_res and i not in conv_ups)
+            out = None if (pair_first or head_cand) else view_for(final)
+            views[i] = out
+            if cv["cout"] % 8 or cin_k % 8:
+                raise Refused("conv %d: channel counts must be multiples of 8 for the HIP path" % i)     # engine.py: the same refusal
+            me = dict(layer=i, xin=xin, cin_k=cin_k, **cv)
+            if pending is not None:
+                first, pending = pending, None
+                a, b = _pair_descs(N, first, me, out.cs)
+                out_recs.append(dict(form="pair", layer=i, descs=(a, b), shortcut=res is not None, code=1,
+                                     name="conv_stem_pair<k%ds%d+k%ds%d%s>" % (first["k"], first["s"], cv["k"], cv["s"], "+res" if res is not None else "")))
+                continue
+            if (not cv["bn"] and cv["act"] == ops.ACT_LINEAR and cv["k"] == 1 and cv["s"] == 1 and res is None and ups == 1 and i + 1 < n and
+                    defs[i + 1]["type"] == "yolo" and readers[i] == [i + 1] and i not in home):
+                yd = defs[i + 1]
+                na, no = len(yolo_mask(yd)), int(yd["classes"]) + 6
+                ht = (N, xin.H, xin.W, xin.C, cv["cout"], 1, 1, 0, xin.cs, cv["cout"], 0, ops.ACT_LINEAR, 0.0, 1, 0)
+                if _L().ryolo_conv_head_decode_supported(C.byref(mk_desc(ht)), na, no):
+                    pending_head = dict(desc=ht, na=na, no=no, cin=xin.C)
+                    views[i] = None
+                    continue
+            if pair_first:
+                nx = _conv(defs[i + 1])
+                res_layer = conv_res.get(i + 1)
+                shortcut = res_layer is not None
+                if nx["bn"] and not (shortcut and views[res_layer] is not xin):
+                    a, b = _pair_descs(N, me, dict(nx, cin_k=cv["cout"]), None)
+                    if _L().ryolo_conv_pair_supported(C.byref(mk_desc(a)), C.byref(mk_desc(b)), 1 if shortcut else 0):
+                        pending = me
+                        continue
+            if out is None:
+                out = view_for(final)
+                views[i] = out
+            dt = (N, xin.H, xin.W, xin.C, cv["cout"], cv["k"], cv["s"], cv["pad"], xin.cs, out.cs, res.cs if res is not None else 0,
+                  cv["act"], cv["slope"], ups, 0)
+            code = _choice(dt, res is not None, False)
+            out_recs.append(dict(form="eval", layer=i, desc=dt, residual=res is not None, code=code,
+                                 name=ops.kernel_name_of(code, cv["k"], cv["s"], cin_k),
+                                 out_off=out.off, res_layer=conv_res.get(i)))
+        elif t in ("shortcut", "upsample", "maxpool"):
+            views[i] = view_for(i)
+        elif t == "route":
+            if i in alias:
+                views[i] = views[alias[i]]
+        elif t == "yolo":
+            if pending_head is not None:
+                hc, pending_head = pending_head, None
+                out_recs.append(dict(form="head", layer=i, desc=hc["desc"], na=hc["na"], no=hc["no"], code=1,
+                                     name="conv_pw<k1,K%d>+decode" % hc["cin"]))
+                views[i] = None
+                continue
+            views[i] = views[i - 1]
+        elif t == "reorg3d":
+            views[i] = views[i - 1]
+    return out_recs
+
+
+def _pair_descs(N, first, second, out_cs):
+    """hip_ops.pair_descs on a buffer stand-in"""
+    x = first["xin"]
+    a = (N, x.H, x.W, x.C, first["cout"], first["k"], first["s"], first["pad"], x.cs, first["cout"], 0, first["act"], first["slope"], 1, 0)
+    h1 = (x.H + 2 * first["pad"] - first["k"]) // first["s"] + 1
+    w1 = (x.W + 2 * first["pad"] - first["k"]) // first["s"] + 1
+    b = (N, h1, w1, first["cout"], second["cout"], second["k"], second["s"], second["pad"], first["cout"], out_cs or second["cout"], 0,
+         second["act"], second["slope"], 1, 0)
+    return a, b
+
+
+# ------------------------------------------------------------------------------------------------ train engine mirror
+def train_blocks(defs, H, W, N):
+    """model/train_engine.py TrainEngine.__init__ + _plan_reduce_fusion: per conv block its descriptor and the four call forms"""
+    n = len(defs)
+    shp = _shapes(defs, H, W, True)
+    readers = _readers(defs)
+    fused_into, conv_res = {}, {}
+    for i, d in enumerate(defs):
+        if d["type"] == "shortcut" and i > 0 and defs[i - 1]["type"] == "convolutional" and readers[i - 1] == [i] \
+                and _abs(i, int(d["from"])) != i - 1 and _conv(defs[i - 1])["bn"]:
+            fused_into[i] = i - 1
+            conv_res[i - 1] = _abs(i, int(d["from"]))
+
+    def new_pair(c, h, w):
+        return _V(c, h, w), _V(c, h, w)
+
+    act, grd = [None] * n, [None] * n
+    home, alias = {}, {}
+    for i, d in enumerate(defs):
+        if d["type"] != "route":
+            continue
+        ls = [_abs(i, int(v)) for v in d["layers"].split(",")]
+        if len(ls) == 1:
+            alias[i] = ls[0]
+            continue
+        c, h, w = shp[i]
+        a, g = new_pair(c, h, w)
+        act[i], grd[i] = a, g
+        off = 0
+        for l in ls:
+            src = l
+            while src in alias:
+                src = alias[src]
+            home[src] = (_V(shp[src][0], h, w, base=a.base, off=off, cs=c), _V(shp[src][0], h, w, base=g.base, off=off, cs=c))
+            off += shp[l][0]
+
+    def pair_for(i):
+        return home[i] if i in home else new_pair(*shp[i])
+
+    x_nhwc = _V(8, H, W)
+    plan, blocks = [], []
+    for i, d in enumerate(defs):
+        t = d["type"]
+        if i in fused_into:
+            act[i], grd[i] = act[fused_into[i]], grd[fused_into[i]]
+            continue
+        if t == "convolutional":
+            cv = _conv(d)
+            xin = x_nhwc if i == 0 else act[i - 1]
+            xin_g = None if i == 0 else grd[i - 1]
+            final = i + 1 if i in conv_res else i
+            y, dy = pair_for(final)
+            if i in conv_res and final not in home:
+                rg = grd[conv_res[i]]
+                if rg is not None and (rg.C, rg.H, rg.W) == (dy.C, dy.H, dy.W) and rg.cs == rg.C:
+                    dy = rg
+            act[i], grd[i] = y, dy
+            c, h, w = shp[i]
+            dt = (N, xin.H, xin.W, xin.C, c, cv["k"], cv["s"], cv["pad"], xin.cs, c, 0, 0, 0.0, 1, 0)
+            recompute = i == 0 and cv["bn"] and i not in conv_res and bool(_L().ryolo_conv0_recompute_supported(C.byref(mk_desc(dt))))
+            one_pass = recompute and xin_g is None
+            blk = dict(layer=i, desc=dt, bn=cv["bn"], prelu=cv["act"] == ops.ACT_LEAKY, recompute=recompute, one_pass=one_pass,
+                       xin_g=xin_g, dy=dy, z_shape=(c, h, w), cin_real=3 if i == 0 else xin.C, residual=i in conv_res)
+            blocks.append(blk)
+            plan.append(("conv", blk))
+        elif t == "shortcut":
+            act[i], grd[i] = pair_for(i)
+            plan.append(("add", None))
+        elif t == "upsample":
+            act[i], grd[i] = pair_for(i)
+            plan.append(("up", None))
+        elif t == "route":
+            if i in alias:
+                act[i], grd[i] = act[alias[i]], grd[alias[i]]
+        elif t == "yolo":
+            act[i], grd[i] = act[i - 1], grd[i - 1]
+            plan.append(("yolo", None))
+    # _plan_reduce_fusion: consecutive backward entries (X, Y) = (plan[k + 1], plan[k])
+    bplan = list(reversed(plan))
+    for (k0, x), (k1, y) in zip(bplan[:-1], bplan[1:]):
+        if k0 != "conv" or k1 != "conv" or x["xin_g"] is None or not y["bn"] or y["recompute"] or not y["prelu"]:
+            continue
+        g, dy = x["xin_g"], y["dy"]
+        if g.ptr() != dy.ptr() or (g.C, g.H, g.W) != (dy.C, dy.H, dy.W) or g.cs != dy.cs or y["z_shape"] != (dy.C, dy.H, dy.W):
+            continue
+        if g.cs != g.C:
+            continue
+        if tr.dgrad_bnreduce_rows(mk_desc(x["desc"])) > 0:
+            x["bnred"] = True
+    recs = []
+    L = _L()
+    for b in blocks:
+        dt = b["desc"]
+        d = mk_desc(dt)
+        code = L.ryolo_conv_kernel_choice(C.byref(d), 0, 1 if b["bn"] else 0)
+        recs.append(dict(form="train", layer=b["layer"], desc=dt, code=code, stats=b["bn"], recompute=b["recompute"],
+                         name=ops.kernel_name_of(code, dt[5], dt[6], dt[3])))
+        if b["xin_g"] is not None:
+            red = bool(b.get("bnred"))
+            code = L.ryolo_conv_dgrad_kernel_choice(C.byref(d), 1 if red else 0)
+            recs.append(dict(form="dgrad", layer=b["layer"], desc=dt, code=code, bnred=red,
+                             name=ops.kernel_name_of(code, dt[5], 1, dt[4])))
+        if not (b["bn"] and b["recompute"] and b["one_pass"]):
+            code = L.ryolo_conv_wgrad_kernel_choice(C.byref(d))
+            recs.append(dict(form="wgrad", layer=b["layer"], desc=dt, code=code, cin_real=b["cin_real"], splits=wgrad_splits(dt, code)))
+    return recs
+
+
+# ------------------------------------------------------------------------------------------------ edge bits
+def _out_hw(t):
+    N, H, W, Cin, Cout, k, s, pad = t[:8]
+    return (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1
+
+
+def _grid_bits(T, grid):
+    """(underfull, ragged last round) of a persistent grid of `grid` workgroups walking T tiles"""
+    return T < grid, T > grid and T % grid != 0
+
+
+def _idle_wgs(code, M, Cout, cus):
+    """conv_mp.hip:657 / conv_mq.hip:713-714: a tile list shorter than the persistent grid shrinks the grid to round8(T) workgroups; when
+    T % 8 != 0 the surplus workgroups of the last XCD chunk exit at once"""
+    if code not in (1, 2, 3, 9, 10):
+        return False
+    bm, bn = {1: (256, 256), 2: (192, 256), 3: (128, 256), 9: (128, 128), 10: (64, 128)}[code]
+    T = -(-M // bm) * -(-Cout // bn)
+    cap = (cus & ~7) if code in (1, 2) else 2 * (cus & ~7)
+    return T < cap and T % 8 != 0
+
+
+def _gemm_bits(code, M, Cout, ks, cus, stats, res, os_, force, kpad):
+    """tile bits of the implicit-GEMM families for one launch of M pixels x Cout channels"""
+    if code in (1, 2):          # conv_mp.hip:655-657 persistent grid of CUs & ~7; BM 256 / 192, BN 256 (MP_BN)
+        bm, bn = (256 if code == 1 else 192), 256
+        T = -(-M // bm) * -(-Cout // bn)
+        return (M % bm != 0, Cout % bn != 0) + _grid_bits(T, cus & ~7)
+    if code == 3:               # conv_mq.hip:706-714 mq_grid_for: 2 x (CUs & ~7) workgroups; 128 x 256 tiles
+        T = -(-M // 128) * -(-Cout // 256)
+        return (M % 128 != 0, Cout % 256 != 0) + _grid_bits(T, 2 * (cus & ~7))
+    if code in (9, 10):         # conv_mq.hip 128-channel tiles (128 / 64 pixels)
+        bm = 128 if code == 9 else 64
+        T = -(-M // bm) * -(-Cout // 128)
+        return (M % bm != 0, Cout % 128 != 0) + _grid_bits(T, 2 * (cus & ~7))
+    if code >= 16:              # conv.hip:1301 igemm_tile_code; 1415-1433 launch_variant's persistent grid
+        bm, bn, waves, nst = {1: (128, 128, 8, 2), 2: (256, 64, 4, 2), 3: (256, 32, 4, 2), 4: (256, 128, 8, 3), 6: (128, 128, 8, 2),
+                              7: (128, 128, 4, 2)}[code - 16]
+        T = -(-M // bm) * -(-Cout // bn)
+        grid = (2 * cus) & ~7
+        # conv.hip:1671-1678: the 1x1 128 x 128 auto pick leaves the persistent layout to the 4-wave tile; conv.hip:1655-1659 force_persist
+        no_persist = code == 17 and ks == 1
+        persist_ok = os_ == 1 and (not stats or (waves == 4 and not res))
+        persistent = False
+        if nst == 2 and bm * bn <= (bm + bn) * BK and persist_ok and not no_persist and (ks == 1 or force):
+            persistent = (T > grid) if force else (2 * T >= 5 * grid)
+        under, ragged = _grid_bits(T, grid) if persistent else (False, False)
+        return (M % bm != 0, Cout % bn != 0, under, ragged)
+    raise KeyError(code)
+
+
+def _pw_bits(M, Cout, Cin, cus, decode_nb=None, bnred=False):
+    """conv_pw.hip:586-627 pw_pick: channel blocks of ncb, row blocks of pf * 16 pixels, grid = wgpc * (CUs & ~7) split over the blocks
+    (bnred: the configurations of the data gradient that carries the folded BatchNorm reduce, conv_pw.hip:606-613)"""
+    kt = Cin // 64
+    c = cus & ~7
+    if decode_nb is not None:
+        ncb, pf, wgpc = (128 if kt == 16 else 256), 4, 1
+        NB = decode_nb
+    else:
+        if kt == 4 and Cout <= 128 and not bnred:
+            ncb, pf, wgpc = 128, 8, 2
+        elif kt == 6 and Cout <= 128 and not bnred:
+            ncb, pf, wgpc = 128, 4, 2
+        elif kt == 2 and Cout % 256 == 0:
+            ncb, pf, wgpc = 256, 4, 1
+        elif kt in (4, 8):
+            ncb, pf, wgpc = (128 if bnred else 256), 4, 1
+        elif kt in (12, 16) and not bnred:
+            ncb, pf, wgpc = 128, 4, 1
+        else:
+            raise ValueError("conv_pw serves no configuration for K %d, C_out %d (bnred %s)" % (Cin, Cout, bnred))
+        NB = -(-Cout // ncb)
+    grid = wgpc * c
+    mb = -(-M // (pf * 16))
+    per_block = grid // max(NB, 1)
+    return (M % (pf * 16) != 0, Cout % ncb != 0) + _grid_bits(mb, per_block)
+
+
+def _spatial_bits(Ho, Wo, N, th, tw, grid):
+    """the halo / stem kernels: tiles of th x tw output pixels on a persistent grid (conv_stem.hip:973-978, 1136-1140, 1146-1151, 1115-1122)"""
+    nt = N * -(-Ho // th) * -(-Wo // tw)
+    return (Wo % tw != 0, Ho % th != 0) + _grid_bits(nt, grid)
+
+
+def wgrad_reduce_kind(S, Cout, cin_real, ks):
+    """train.hip wgrad_reduce_kind: the split-K reduce a layer takes -- 0 one element per thread, 1 four split quarters per workgroup
+    (S >= 8), 2 the transposing 3x3 kernel (few splits, >= 2^20 weights)"""
+    total = Cout * cin_real * ks * ks
+    if S < 8 and ks == 3 and cin_real % 64 == 0 and total >= (1 << 20):
+        return 2
+    return 1 if S >= 8 else 0
+
+
+def wgrad_splits(t, code):
+    ws = _L().ryolo_conv_wgrad_workspace_bytes(C.byref(mk_desc(t)))
+    N, H, W, Cin, Cout, k = t[:6]
+    kpad = -(-(k * k * Cin) // 64) * 64
+    per = (Cout * kpad * 4) if code > WGRAD_TAPS else (-(-Cout // 128) * 128 * kpad * 4)
+    assert ws % per == 0, (t, ws, per)
+    return ws // per
+
+
+def edge_bits(rec, cus):
+    """named boolean edge bits of one census record"""
+    form, code, t = rec["form"], rec["code"], rec.get("desc")
+    if form == "pair":
+        a, b = rec["descs"]
+        Ho, Wo = _out_hw(b)
+        # conv_stem.hip:28/33 (P<1>: 8 x 32 tiles), 573-600; grid 2 x CUs
+        return dict(zip(("part_right", "part_bottom", "underfull", "ragged"), _spatial_bits(Ho, Wo, b[0], 8, 32, (2 * cus) & ~7)))
+    N, H, W, Cin, Cout, k, s, pad, in_cs, out_cs = t[:10]
+    Ho, Wo = _out_hw(t)
+    names4 = ("part_m", "part_n", "underfull", "ragged")
+    if form == "head":
+        # conv_pw.hip:593-601: the decoded head: all anchors' channels in NB blocks, grid = CUs & ~7
+        apb = (128 if Cin == 1024 else 256) // rec["no"]          # conv_pw.hip pw_decode_apb: whole anchors per channel block
+        nb = -(-rec["na"] // apb)
+        return dict(zip(names4, _pw_bits(N * H * W, Cout, Cin, cus, decode_nb=nb)))
+    if form == "wgrad":
+        M = N * Ho * Wo
+        S = rec["splits"]
+        if code > WGRAD_TAPS:
+            # train.hip:1438-1453: K steps are 64-pixel row segments, `per` steps per split
+            nsteps = N * Ho * -(-Wo // KP)
+            per = -(-nsteps // S)
+            return dict(ragged_split=nsteps % per != 0, part_row=Wo % KP != 0, short_row=Wo < KP, multi_split=S > 1,
+                        reduce=wgrad_reduce_kind(S, Cout, rec["cin_real"], k))
+        # train.hip:1454-1564: chunk = ceil(M / S) rounded up to KP pixels; T the c_out tile (256 wide / 258-260 three-stage / square)
+        chunk = -(-(-(-M // S)) // KP) * KP if S > 0 else M
+        tco = 256 if code == 256 else (128 if code in (257, 258, 259) else (64 if code == 260 else code))
+        return dict(ragged_split=M % chunk != 0, short_row=Wo < KP, part_k=M % KP != 0, part_co=Cout % tco != 0, multi_split=S > 1,
+                    reduce=wgrad_reduce_kind(S, Cout, rec["cin_real"], k))
+    if form in ("eval", "train"):
+        stats = form == "train" and rec["stats"]
+        res = form == "eval" and rec["residual"]
+        if code == 4:            # conv.hip:1765-1773: 16-pixel groups, 32 groups per wave, 4 waves per block
+            M = N * Ho * Wo
+            return dict(part_group=M % 16 != 0, part_block=M % (16 * 32 * 4) != 0)
+        if code == 8:            # conv_stem.hip:232 (8 x 64 tiles), 1136-1140 grid 4 x CUs
+            return dict(zip(("part_right", "part_bottom", "underfull", "ragged"), _spatial_bits(Ho, Wo, N, 8, 64, (4 * cus) & ~7)))
+        if code == 5:            # conv_stem.hip:28-33: 8 x 32 (stride 1) / 4 x 32 (stride 2)
+            return dict(zip(("part_right", "part_bottom", "underfull", "ragged"),
+                            _spatial_bits(Ho, Wo, N, 8 if s == 1 else 4, 32, (2 * cus) & ~7)))
+        if code == 11:           # conv_stem.hip:741 (4 x 32 tiles), 973-978
+            return dict(zip(("part_right", "part_bottom", "underfull", "ragged"), _spatial_bits(Ho, Wo, N, 4, 32, (2 * cus) & ~7)))
+        M = N * Ho * Wo
+        if code == 6:
+            return dict(zip(names4, _pw_bits(M, Cout, Cin, cus)))
+        kpad = -(-(k * k * Cin) // BK) * BK
+        force = k == 3 and kpad // BK <= 9 and not (stats and (res or code == 18))    # conv.hip:1655-1659
+        bits = _gemm_bits(code, M, Cout, k, cus, stats, res, 1, force, kpad)
+        return dict(zip(names4, bits), part_cstride=out_cs != Cout, idle_wgs=_idle_wgs(code, M, Cout, cus))
+    if form == "dgrad":
+        if code == 7:            # conv_stem.hip:1115-1122 (8 x 64 stride 2 / 4 x 32 stride 1 / 8 x 32 the 128-channel kernel)
+            th, tw = (8, 64) if (Cin == 32 and s == 2) else ((4, 32) if Cin == 32 else (8, 32))
+            return dict(zip(("part_right", "part_bottom", "underfull", "ragged"), _spatial_bits(H, W, N, th, tw, (2 * cus) & ~7)))
+        # conv.hip:2481-2546: stride 1 is one launch over the input pixels; stride 2 is two x-fused classes (pixel pairs, 2 C_in channels)
+        # or four parity classes, each a launch with its own pixel count
+        launches = []
+        if s == 1:
+            launches.append((N * H * W, Cin, 1))
+        elif Cin <= 64 and Cin % 32 == 0 and W % 2 == 0 and in_cs == Cin:
+            launches += [(N * ((H - a + 1) // 2) * (W // 2), 2 * Cin, 2) for a in (0, 1)]
+        else:
+            launches += [(N * ((H - a + 1) // 2) * ((W - b + 1) // 2), Cin, 2) for a in (0, 1) for b in (0, 1)]
+        acc = [False] * 5
+        for M, co, os_ in launches:
+            if M <= 0:
+                continue
+            if code == 6:
+                bits = _pw_bits(M, co, Cout, cus, bnred=rec["bnred"]) + (False,)
+            else:
+                kpad = -(-(k * k * Cout) // BK) * BK
+                force = k == 3 and os_ == 1 and kpad // BK <= 9 and not rec["bnred"]
+                bits = _gemm_bits(code, M, co, k, cus, False, False, os_, force, kpad) + (_idle_wgs(code, M, co, cus),)
+            acc = [x or y for x, y in zip(acc, bits)]
+        return dict(zip(names4 + ("idle_wgs",), acc), multi_launch=len(launches) > 1)
+    raise KeyError(form)
+
+
+def edge_class(rec, cus):
+    t = rec.get("desc") or rec["descs"][1]
+    bits = edge_bits(rec, cus)
+    extra = ()
+    if rec["form"] == "dgrad":
+        extra = (("bnred", rec["bnred"]),)
+    elif rec["form"] == "train":
+        extra = (("stats", rec["stats"]), ("recompute", rec["recompute"]))
+    elif rec["form"] == "eval":
+        extra = (("residual", rec["residual"]), ("ups", t[13] == 2))
+    return (rec["form"], rec["code"], t[5], t[6]) + extra + tuple(sorted(bits.items()))
+
+
+def cost(rec):
+    """M * K * C_out of the record's launch (the representative is the cheapest point of a class)"""
+    t = rec.get("desc") or rec["descs"][1]
+    Ho, Wo = _out_hw(t)
+    return t[0] * Ho * Wo * t[5] * t[5] * t[3] * t[4]
+
+
+def census(cus=256, configs=CONFIGS, sizes=SIZES, batches=BATCHES, refused=None):
+    """{edge class: dict(count, rep)} over the input space; rep = the cheapest record reaching the class (ties: first seen).
+    Points the engines refuse at plan time are skipped and listed in `refused` (a list, when given)."""
+    classes = {}
+    for kind, nc in configs:
+        for (H, W) in sizes:
+            defs = config_defs(kind, nc, H, W)
+            for N in batches:
+                try:
+                    recs = eval_blocks(defs, H, W, N)
+                except Refused as e:
+                    if refused is not None:
+                        refused.append(((kind, nc, H, W, N), str(e)))
+                    continue
+                if kind == "darknet53":
+                    recs += train_blocks(defs, H, W, N)
+                for r in recs:
+                    r["point"] = (kind, nc, H, W, N)
+                    key = edge_class(r, cus)
+                    e = classes.get(key)
+                    if e is None:
+                        classes[key] = dict(count=1, rep=r)
+                    else:
+                        e["count"] += 1
+                        if cost(r) < cost(e["rep"]):
+                            e["rep"] = r
+    return classes
+
+
+def format_table(classes):
+    rows = []
+    for key in sorted(classes, key=lambda k: (k[0], k[1], k[2], k[3], str(k[4:]))):
+        e = classes[key]
+        r = e["rep"]
+        t = r.get("desc") or r["descs"][1]
+        bits = ",".join(k if v is True else "%s=%s" % (k, v) for k, v in key[4:] if v) or "-"
+        rows.append("%-6s code %-4d k%d s%d  %-60s  n=%-5d rep %s layer %d  desc N%d %dx%d %d->%d cs %d/%d" % (
+            key[0], key[1], key[2], key[3], bits, e["count"], r["point"], r["layer"], t[0], t[1], t[2], t[3], t[4], t[8], t[9]))
+    return "\n".join(rows)

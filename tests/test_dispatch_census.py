@@ -1,0 +1,65 @@
+"""CPU tier: the dispatch census (tests/dispatch_census.py) runs without a GPU (the library's kernel-choice calls are dry runs;
+its CU count falls back to 256, the MI355X's), is deterministic, gives every edge class a representative, and names at 608^2 / bs 64
+the kernels test_train_engine_gpu.py asserts of the training engine at that size."""
+import ctypes as C
+
+from tests import dispatch_census as dc
+
+
+def _key(r):
+    t = r["desc"]
+    return "k%d s%d %d->%d @%d" % (t[5], t[6], t[3], t[4], dc._out_hw(t)[0])
+
+
+def test_census_runs_is_deterministic_and_every_class_has_a_representative():
+    refused = []
+    a = dc.census(cus=256, refused=refused)
+    b = dc.census(cus=256)
+    assert list(a) == list(b)
+    assert all(a[k]["count"] == b[k]["count"] and a[k]["rep"]["point"] == b[k]["rep"]["point"] for k in a)
+    forms = set(k[0] for k in a)
+    assert forms == {"eval", "pair", "head", "train", "dgrad", "wgrad"}, forms
+    for key, e in a.items():
+        r = e["rep"]
+        assert e["count"] >= 1 and r["code"] >= 0, key
+        assert dc.edge_class(r, 256) == key
+    # yolov3-tiny with one class has 252-channel heads: the engine refuses it (channel counts must be multiples of 8)
+    assert refused and all(p[0] == "tiny" and p[1] == 1 for p, _ in refused)
+    print("\n%d edge classes" % len(a))
+
+
+def test_census_names_the_bs64_kernels_the_engine_test_asserts():
+    defs = dc.config_defs("darknet53", 1, 608, 608)
+    recs = dc.train_blocks(defs, 608, 608, 64)
+    fwd = {_key(r): dc.ops.kernel_name_of(r["code"], r["desc"][5], r["desc"][6], r["desc"][3]) for r in recs if r["form"] == "train"}
+    dgr = {_key(r): dc.ops.kernel_name_of(r["code"], r["desc"][5], 1, r["desc"][4]) for r in recs if r["form"] == "dgrad"}
+    assert fwd["k3 s1 128->256 @76"] == 'conv_mq<k3,128x256>' and fwd["k3 s1 256->512 @38"] == 'conv_mq<k3,128x256>'
+    assert dgr["k3 s1 256->512 @38"] == 'conv_mq<k3,128x256>'
+    assert fwd["k3 s1 64->128 @152"] == 'conv3x3_c64_halo' and fwd["k3 s2 64->128 @152"].startswith('conv_igemm<k3,128x128'), fwd
+    assert dgr["k3 s1 128->256 @76"] == 'conv_igemm<k3,128x128>', dgr
+    assert sum(1 for r in recs if r["form"] == "dgrad" and r["bnred"]) >= 40
+    # 75 conv blocks; every one but layer 0 (one-pass backward) has a weight gradient and a data gradient
+    assert sum(r["form"] == "train" for r in recs) == 75
+    assert sum(r["form"] == "dgrad" for r in recs) == 74 and sum(r["form"] == "wgrad" for r in recs) == 74
+
+
+def test_census_examples_of_the_issue():
+    """the dry runs quoted when the census was asked for: bs 16 3x3 128->256 @76 (forward conv_mq, data gradient on the 128 x 128 tile,
+    weight gradient on the wide tile), bs 1 3x3 512->1024 @10 (conv_mq with fewer tiles than workgroups), the nc = 2 head's weight
+    gradient on the square 128 tile (not the 256-row one the 504-channel heads take)"""
+    recs = dc.train_blocks(dc.config_defs("darknet53", 1, 608, 608), 608, 608, 16)
+    by = {(r["form"], _key(r)): r for r in recs}
+    assert dc.ops.kernel_name_of(by[("train", "k3 s1 128->256 @76")]["code"], 3, 1, 128) == 'conv_mq<k3,128x256>'
+    assert by[("dgrad", "k3 s1 128->256 @76")]["code"] == 17
+    assert by[("wgrad", "k3 s1 128->256 @76")]["code"] == 256
+    recs = dc.train_blocks(dc.config_defs("darknet53", 1, 320, 320), 320, 320, 1)
+    r = [r for r in recs if r["form"] == "train" and _key(r) == "k3 s1 512->1024 @10"][0]
+    assert r["code"] == 3 and dc.edge_bits(r, 256)["underfull"]
+    recs = dc.train_blocks(dc.config_defs("darknet53", 2, 608, 608), 608, 608, 16)
+    heads = [r for r in recs if r["form"] == "wgrad" and r["desc"][4] == 576]
+    assert len(heads) == 3 and all(r["code"] == 128 for r in heads)
+    recs = dc.train_blocks(dc.config_defs("darknet53", 1, 608, 608), 608, 608, 16)
+    assert all(r["code"] == 256 for r in recs if r["form"] == "wgrad" and r["desc"][4] == 504)
+    L = dc._L()
+    d = dc.mk_desc(heads[0]["desc"])
+    assert L.ryolo_conv_wgrad_kernel_choice(C.byref(d)) == 128

@@ -72,21 +72,43 @@ def test_tiny_engine_vs_oracle(cuda_dev):
     _cmp("tiny io", io, io_o, rel_max=0.015, rel_mean=0.0025)
 
 
-def test_full_size_608_vs_oracle(cuda_dev):
-    cfg = make_cfg.darknet53()
+def _full_size_vs_oracle(cuda_dev, cfg, bs, h, w, seed):
+    """the product path (Darknet.forward -> HipEngine) at a full input size against the oracle's forward: every head, the decoded rows"""
     m, mg = _model(cfg, cuda_dev)
-    x = torch.rand(2, 3, 608, 608, generator=torch.Generator().manual_seed(7))
+    x = torch.rand(bs, 3, h, w, generator=torch.Generator().manual_seed(seed))
     with torch.no_grad():
         io, p = mg(x.to(cuda_dev))
-    assert io.shape == (2, 545832, 7)
+    no = m.nc + 6
+    assert io.shape == (bs, 72 * (h * w // 32 ** 2 + h * w // 16 ** 2 + h * w // 8 ** 2), no), io.shape
     sd = {k: v.cpu() for k, v in m.state_dict().items()}
     io_o, p_o = do.forward(cfg, sd, x, bf16=True)
-    _cmp("608 io", io, io_o, rel_max=0.02, rel_mean=0.0025)
-    _cmp("608 p2", p[2], p_o[2], rel_max=0.015, rel_mean=0.0025)
+    tag = "%dx%d" % (h, w)
+    _cmp(tag + " io", io, io_o, rel_max=0.02, rel_mean=0.0025)
+    for k in range(3):
+        _cmp("%s p%d" % (tag, k), p[k], p_o[k], rel_max=0.015, rel_mean=0.0025)
+    return mg, x, io
+
+
+def test_full_size_608_vs_oracle(cuda_dev):
+    mg, x, io = _full_size_vs_oracle(cuda_dev, make_cfg.darknet53(), 2, 608, 608, 7)
+    assert io.shape == (2, 545832, 7)
     # batch independence (size-independent property): image 1 alone gives the same rows, bit for bit
     with torch.no_grad():
         io1, _ = mg(x[1:].to(cuda_dev))
     assert torch.equal(io1[0], io[1])
+
+
+@pytest.mark.parametrize("h,w", [(512, 512), (416, 640)])
+def test_full_size_vs_oracle_at_the_default_and_a_rectangular_size(cuda_dev, h, w):
+    """train.py's default 512^2 and a rectangular 416 x 640 input (13 x 20 cells at stride 32), bs 1: the batch-dependent dispatch,
+    the route-concat placement, the fused residuals / upsamples and the head row offsets at shapes the 608^2 case does not reach"""
+    _full_size_vs_oracle(cuda_dev, make_cfg.darknet53(w, h), 1, h, w, 8)
+
+
+def test_fifteen_class_heads_vs_oracle_320(cuda_dev):
+    """darknet53(classes=15): 1512-channel heads (no = 21; the fused head decode serves no <= 8, so these run the conv tiles and the
+    separate decode) against the oracle at 320^2"""
+    _full_size_vs_oracle(cuda_dev, make_cfg.darknet53(320, 320, classes=15), 1, 320, 320, 9)
 
 
 def test_configs1_bs32_608_forward_equals_the_oracle_checked_bs2_rows(cuda_dev):

@@ -210,17 +210,16 @@ class _Checker(object):
                 assert not bool(bad.any()), (what, float((got - ref).abs().max()), float(tol.max()), float(ref.abs().max()))
 
 
-def _one_step(cuda_dev, bs, rep):
+def _one_step(cuda_dev, bs, rep, height=608, width=608):
     torch.backends.cudnn.allow_tf32 = False          # the references are plain fp32
     torch.backends.cuda.matmul.allow_tf32 = False
-    size = 608
-    cfg = make_cfg.darknet53(size, size)
+    cfg = make_cfg.darknet53(width, height)
     hyp = dict(HYP)
     hyp["riou"] = 1
     model = _well_conditioned(Darknet(cfg, hyp)).to(cuda_dev).train()
     model.nc, model.arc = 1, "default"
     model._engines = {}
-    x4 = torch.rand(bs // rep, 3, size, size, generator=torch.Generator().manual_seed(11)).to(cuda_dev)
+    x4 = torch.rand(bs // rep, 3, height, width, generator=torch.Generator().manual_seed(11)).to(cuda_dev)
     tg4 = synthetic_targets(bs // rep, seed=12, device=cuda_dev)
     x = x4.repeat(rep, 1, 1, 1)
     tg = torch.cat([tg4 + torch.tensor([float(bs // rep) * r, 0, 0, 0, 0, 0, 0], device=cuda_dev) for r in range(rep)])
@@ -256,3 +255,16 @@ def test_every_block_of_the_backward_plan_alone_bs64_608(cuda_dev):
     assert chk.checked['bn_reduced'] >= 30 and chk.checked['dgrad_bnreduce'] == chk.checked['bn_reduced'], chk.checked
     assert eng.batch_reduce        # the split-K reduces ran as one launch per segment
     print("bs 64: 75/75 conv blocks; %d blocks took the folded BatchNorm reduce" % chk.checked['bn_reduced'])
+
+
+@pytest.mark.parametrize("bs,rep,height,width", [(16, 4, 512, 512), (4, 1, 416, 640)])
+def test_every_block_of_the_backward_plan_alone_at_other_sizes(cuda_dev, bs, rep, height, width):
+    """train.py's default size (512^2, bs 16 = four images x 4) and a rectangular input (416 x 640, 13 x 20 cells at stride 32): the
+    shape-driven dispatch takes other tiles, grids and split counts there than at 608^2"""
+    eng, chk = _one_step(cuda_dev, bs, rep, height, width)
+    nconv = sum(1 for kind, _, _, _ in eng.bplan if kind == 'conv')
+    assert nconv == 75 and chk.checked['conv'] == 75, chk.checked
+    assert chk.checked['add'] + chk.checked['up'] == sum(1 for kind, _, _, _ in eng.bplan if kind in ('add', 'up'))
+    assert chk.checked['up'] == 2
+    print("bs %d %dx%d: 75/75 conv blocks, %d shortcut, %d upsample entries; %d blocks with the folded BatchNorm reduce"
+          % (bs, height, width, chk.checked['add'], chk.checked['up'], chk.checked['bn_reduced']))

@@ -12,7 +12,19 @@ LIB_PATH = os.environ.get("RYOLO_HIP_LIB") or os.path.join(_HERE, "libryolo_hip.
 
 _lib = None
 
+ACT_LINEAR, ACT_LEAKY, ACT_MISH = 0, 1, 2
+
+
+class ConvDesc(C.Structure):
+    """ryolo_conv_desc of include/ryolo.h"""
+    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int),
+                ("ksize", C.c_int), ("stride", C.c_int), ("pad", C.c_int),
+                ("in_cstride", C.c_int), ("out_cstride", C.c_int), ("res_cstride", C.c_int),
+                ("act", C.c_int), ("slope", C.c_float), ("upsample", C.c_int), ("tile", C.c_int)]
+
+
 _vp = C.c_void_p
+_dp = C.POINTER(ConvDesc)
 _sigs = {
     "ryolo_strerror": (C.c_char_p, [C.c_int]),
     "ryolo_abi_version": (C.c_int, []),
@@ -27,6 +39,11 @@ _sigs = {
     "ryolo_rnms_count_pairs": (None, [_vp]),
     "ryolo_skew_iou_pairs": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
     "ryolo_skew_iou_matrix": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
+    # the dry-run queries of the layer planner (model/plan.py)
+    "ryolo_conv_pair_supported": (C.c_int, [_dp, _dp, C.c_int]),
+    "ryolo_conv_head_decode_supported": (C.c_int, [_dp, C.c_int, C.c_int]),
+    "ryolo_conv0_recompute_supported": (C.c_int, [_dp]),
+    "ryolo_conv2d_dgrad_bnreduce_rows": (C.c_int, [_dp]),
 }
 
 

@@ -9,22 +9,12 @@ import ctypes as C
 import torch
 
 from .. import _lib
-
-ACT_LINEAR, ACT_LEAKY, ACT_MISH = 0, 1, 2
-
-
-class ConvDesc(C.Structure):
-    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int),
-                ("ksize", C.c_int), ("stride", C.c_int), ("pad", C.c_int),
-                ("in_cstride", C.c_int), ("out_cstride", C.c_int), ("res_cstride", C.c_int),
-                ("act", C.c_int), ("slope", C.c_float), ("upsample", C.c_int), ("tile", C.c_int)]
-
+from .._lib import ACT_LEAKY, ACT_LINEAR, ACT_MISH, ConvDesc  # noqa: F401  (part of this module's interface)
 
 _vp = C.c_void_p
 _lib.declare("ryolo_conv_packed_weight_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int])
 _lib.declare("ryolo_conv_pack_weights", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp])
 _lib.declare("ryolo_conv2d_bn_act", C.c_int, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp])
-_lib.declare("ryolo_conv_pair_supported", C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), C.c_int])
 _lib.declare("ryolo_conv2d_bn_act_pair", C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp])
 _lib.declare("ryolo_conv_kernel_choice", C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int])
 _lib.declare("ryolo_conv_dgrad_kernel_choice", C.c_int, [C.POINTER(ConvDesc), C.c_int])

@@ -22,7 +22,6 @@ _lib.declare("ryolo_conv_packed_dgrad_bytes", C.c_size_t, [C.c_int, C.c_int, C.c
 _lib.declare("ryolo_conv_pack_weights_dgrad", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp])
 _lib.declare("ryolo_conv_dgrad_tap_table", C.c_int, [C.c_int, C.c_int, _vp])
 _lib.declare("ryolo_conv2d_dgrad", C.c_int, [_P, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp])
-_lib.declare("ryolo_conv2d_dgrad_bnreduce_rows", C.c_int, [_P])
 _lib.declare("ryolo_conv2d_dgrad_bnreduce", C.c_int, [_P, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp,
                                                       _vp, _vp])
 _lib.declare("ryolo_bn_act_bwd_reduced", C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int,
@@ -200,7 +199,6 @@ def conv_fwd_stats(d, x, packed_w, ones, shift, z, part=None, clear=True):
     return part
 
 
-_lib.declare("ryolo_conv0_recompute_supported", C.c_int, [C.POINTER(ConvDesc)])
 _lib.declare("ryolo_conv0_bn_act_fwd", C.c_int, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp])
 _lib.declare("ryolo_conv0_bn_bwd_workspace_bytes", C.c_size_t, [])
 _lib.declare("ryolo_conv0_bn_bwd", C.c_int, [C.POINTER(ConvDesc), _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int,

@@ -1,0 +1,393 @@
+"""Layer planner -- the rules that turn a Darknet cfg into buffers and launches, once, on plain Python data.
+
+No tensor is allocated and no device is touched here: HipEngine (model/engine.py) and TrainEngine (model/train_engine.py)
+materialise a plan into tensors and closures, tests/dispatch_census.py walks the same plans without a GPU.  The only calls
+into the library are its dry-run queries (pair / fused head / layer-0 recompute supported, rows of the folded BatchNorm reduce).
+
+Input: the cfg `defs` (without the `net` block), batch and input size, `convs[i]` = dict(cout, k, s, pad, bn, act, slope) of
+every `convolutional` layer (the engines read them from the modules: a fused model has lost its BatchNorm modules while its
+defs still say batch_normalize=1; a `refuse` message in it is raised when the walk reaches that layer), `yolos[i]` = (na, no).
+
+A `View` is a channel slice of a buffer: (buffer id, channel offset, C, H, W, pixel stride); `buffers[id]` = (C, H, W) of the
+NHWC bf16 allocation, buffer 0 is the 8-channel network input.  Two views are the same tensor exactly when they are equal.
+
+The plan of both engines:
+  * `shortcut` layers are folded into the producing conv as a residual operand, `upsample` x2 into its store (inference only);
+  * sources of a multi-input `route` are written into channel slices ("homes") of the route's concat buffer by whoever
+    produces them; single-input routes are aliases;
+and, where the two differ, one explicit policy each: inference falls back to run-time copies / the small NHWC kernels and fuses
+stem pairs and YOLO heads; training refuses what it has no kernels for, mirrors every activation buffer with a gradient buffer,
+shares one gradient buffer along a residual chain and decides statically who writes a gradient view first.
+"""
+import ctypes as C
+from collections import namedtuple
+
+from .. import _lib
+from .._lib import ACT_LINEAR, ConvDesc
+
+View = namedtuple('View', 'buf off C H W cs')
+EvalPlan = namedtuple('EvalPlan', 'shapes buffers x views ops')
+TrainPlan = namedtuple('TrainPlan', 'shapes buffers x act grd forward blocks backward')
+
+
+class Refused(RuntimeError):
+    """the configuration is refused at plan time (as opposed to a bug in the planner)"""
+
+
+def _abs(i, l):
+    return l if l > 0 else i + l      # route/shortcut index convention of models.py:101-114 (0 is "relative")
+
+
+def _sources(i, d):
+    return [_abs(i, int(v)) for v in d['layers'].split(',')]
+
+
+def _new(buffers, c, h, w):
+    buffers.append((c, h, w))
+    return View(len(buffers) - 1, 0, c, h, w, c)
+
+
+def _slice(v, off, c):
+    return View(v.buf, v.off + off, c, v.H, v.W, v.cs)
+
+
+def _shapes(defs, convs, cin, H, W):
+    """(C, H, W) per layer"""
+    shp = []
+    c, h, w = cin, H, W
+    for i, d in enumerate(defs):
+        t = d['type']
+        if t == 'convolutional':
+            cv = convs[i]
+            c, h, w = cv['cout'], (h + 2 * cv['pad'] - cv['k']) // cv['s'] + 1, (w + 2 * cv['pad'] - cv['k']) // cv['s'] + 1
+        elif t == 'maxpool':
+            k, s = int(d['size']), int(d['stride'])
+            if not (k == 2 and s == 1):
+                p = (k - 1) // 2
+                h, w = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
+        elif t == 'upsample':
+            s = int(d['stride'])
+            h, w = h * s, w * s
+        elif t == 'route':
+            ls = _sources(i, d)
+            c = sum(shp[l][0] for l in ls)
+            h, w = shp[ls[0]][1], shp[ls[0]][2]
+        shp.append((c, h, w))
+    return shp
+
+
+def _readers(defs):
+    """who reads what (decides which epilogue fusions are legal)"""
+    readers = [[] for _ in defs]
+    for i, d in enumerate(defs):
+        if d['type'] == 'route':
+            for l in _sources(i, d):
+                readers[l].append(i)
+        else:
+            if i > 0:
+                readers[i - 1].append(i)
+            if d['type'] == 'shortcut':
+                readers[_abs(i, int(d['from']))].append(i)
+    return readers
+
+
+def _routes(defs, shp):
+    """alias: single-input route -> its source; concat: multi-input route -> [(source with aliases resolved, channel offset)]"""
+    alias, concat = {}, {}
+    for i, d in enumerate(defs):
+        if d['type'] != 'route':
+            continue
+        ls = _sources(i, d)
+        if len(ls) == 1:
+            alias[i] = ls[0]
+            continue
+        off = 0
+        concat[i] = []
+        for l in ls:
+            src = l
+            while src in alias:
+                src = alias[src]
+            concat[i].append((src, off))
+            off += shp[l][0]
+    return alias, concat
+
+
+def _query(name, *descs_then_ints):
+    args = [C.byref(ConvDesc(*a)) if isinstance(a, tuple) else a for a in descs_then_ints]
+    return getattr(_lib.lib(), name)(*args)
+
+
+def pair_descs(N, x, first, second, out_cs=None):
+    """descriptor tuples of a fused stem pair reading view `x`: the tensor between the two convs is dense and never stored"""
+    a = (N, x.H, x.W, x.C, first['cout'], first['k'], first['s'], first['pad'], x.cs, first['cout'], 0, first['act'], first['slope'], 1, 0)
+    h1 = (x.H + 2 * first['pad'] - first['k']) // first['s'] + 1
+    w1 = (x.W + 2 * first['pad'] - first['k']) // first['s'] + 1
+    b = (N, h1, w1, first['cout'], second['cout'], second['k'], second['s'], second['pad'], first['cout'], out_cs or second['cout'], 0,
+         second['act'], second['slope'], 1, 0)
+    return a, b
+
+
+# ------------------------------------------------------------------------------------------------ inference
+def plan_eval(defs, convs, yolos, N, H, W, stem_pair=True, head_decode=True, cin=3):
+    """EvalPlan(shapes, buffers, x, views, ops).  views[i]: the layer's output view, None where the tensor only lives in LDS (first
+    layer of a fused pair) or is materialised on demand (fused head).  ops: dicts in launch order, kind =
+      conv      layer, xin, out, res (view or None), res_layer, ups, desc
+      pair      layer (the second conv), first, xin, out, shortcut, descs, name
+      head      layer (the yolo layer), conv, xin, desc, na, no, name
+      add       layer, a, b, out            upsample  layer, xin, out, stride        maxpool   layer, xin, out, size, stride
+      copy      layer (the route), xin, out  decode    layer, xin
+    descriptors are tuples in ConvDesc field order."""
+    n = len(defs)
+    shp = _shapes(defs, convs, cin, H, W)
+    for i, d in enumerate(defs):
+        if d['type'] == 'route' and any(shp[l][1:] != shp[i][1:] for l in _sources(i, d)):
+            raise Refused("route %d joins tensors of different spatial size (reorg is out of scope)" % i)
+        if d['type'] == 'shortcut' and shp[_abs(i, int(d['from']))] != shp[i - 1]:
+            raise Refused("shortcut %d adds tensors of different shape" % i)
+    readers = _readers(defs)
+    fused_into = {}     # follower layer (shortcut / upsample) -> conv layer that computes it
+    conv_res, conv_ups = {}, set()
+    for i, d in enumerate(defs):
+        if i == 0 or defs[i - 1]['type'] != 'convolutional' or readers[i - 1] != [i] or (i - 1) in fused_into.values():
+            continue
+        if d['type'] == 'shortcut' and _abs(i, int(d['from'])) != i - 1:
+            fused_into[i] = i - 1
+            conv_res[i - 1] = _abs(i, int(d['from']))
+        elif d['type'] == 'upsample' and int(d['stride']) == 2:
+            fused_into[i] = i - 1
+            conv_ups.add(i - 1)
+
+    # homes: sources of multi-input routes live inside the route's concat buffer; the rest is copied at run time
+    buffers = []
+    x = _new(buffers, 8, H, W)
+    views = [None] * n
+    alias, concat = _routes(defs, shp)
+    home, copies = {}, {}
+    for i, srcs in concat.items():
+        views[i] = _new(buffers, *shp[i])
+        for src, off in srcs:
+            if src not in home and defs[src]['type'] in ('convolutional', 'shortcut', 'upsample', 'maxpool') and src < i \
+                    and shp[src][0] % 8 == 0 and off % 8 == 0:
+                home[src] = _slice(views[i], off, shp[src][0])
+            else:
+                copies.setdefault(i, []).append((src, off))
+
+    def view_for(i):
+        return home[i] if i in home else _new(buffers, *shp[i])
+
+    ops = []
+    pending = None       # first layer of a fused stem pair, waiting for its successor
+    pending_head = None  # last conv of a YOLO head, emitted together with its decode
+    for i, d in enumerate(defs):
+        t = d['type']
+        if i in fused_into:
+            views[i] = views[fused_into[i]]        # the conv already produced this layer's tensor
+            continue
+        if t == 'convolutional':
+            cv = convs[i]
+            if cv.get('refuse'):
+                raise Refused(cv['refuse'])
+            xin = x if i == 0 else views[i - 1]    # (None behind the first layer of a fused pair)
+            cin_k = convs[pending['layer']]['cout'] if pending is not None else xin.C
+            res = views[conv_res[i]] if i in conv_res else None
+            ups = 2 if i in conv_ups else 1
+            final = i + 1 if (i in conv_res or i in conv_ups) else i
+            if cv['cout'] % 8 or cin_k % 8:
+                raise Refused("conv %d: channel counts must be multiples of 8 for the HIP path" % i)
+            if pending is not None:
+                # second layer of a fused stem pair (csrc/conv_stem.hip): the first layer's tensor is computed into LDS, never stored
+                first, pending = pending, None
+                fc = convs[first['layer']]
+                views[i] = out = view_for(final)
+                ops.append(dict(kind='pair', layer=i, first=first['layer'], xin=first['xin'], out=out, shortcut=res is not None,
+                                descs=pair_descs(N, first['xin'], fc, cv, out.cs),
+                                name='conv_stem_pair<k%ds%d+k%ds%d%s>' % (fc['k'], fc['s'], cv['k'], cv['s'], '+res' if res is not None else '')))
+                continue
+            alone = readers[i] == [i + 1] and i not in home and res is None and ups == 1
+            if (head_decode and alone and not cv['bn'] and cv['act'] == ACT_LINEAR and cv['k'] == 1 and cv['s'] == 1 and
+                    defs[i + 1]['type'] == 'yolo'):
+                # a YOLO head: conv + decode in one launch (ryolo_conv_head_decode)
+                na, no = yolos[i + 1]
+                ht = (N, xin.H, xin.W, xin.C, cv['cout'], 1, 1, 0, xin.cs, cv['cout'], 0, ACT_LINEAR, 0.0, 1, 0)
+                if _query('ryolo_conv_head_decode_supported', ht, int(na), int(no)):
+                    pending_head = dict(kind='head', conv=i, xin=xin, desc=ht, na=na, no=no, name='conv_pw<k1,K%d>+decode' % xin.C)
+                    continue
+            if (stem_pair and alone and i not in conv_res and defs[i + 1]['type'] == 'convolutional' and (i + 1) not in conv_ups
+                    and convs[i + 1]['bn']):
+                nx = convs[i + 1]
+                if nx.get('refuse'):
+                    raise Refused(nx['refuse'])
+                # a shortcut behind the pair must come from the first layer's own input (it is taken from the LDS image)
+                if (i + 1) not in conv_res or views[conv_res[i + 1]] == xin:
+                    a, b = pair_descs(N, xin, cv, nx)
+                    if _query('ryolo_conv_pair_supported', a, b, 1 if (i + 1) in conv_res else 0):
+                        pending = dict(layer=i, xin=xin)         # emitted together with layer i + 1
+                        continue
+            views[i] = out = view_for(final)
+            desc = (N, xin.H, xin.W, xin.C, cv['cout'], cv['k'], cv['s'], cv['pad'], xin.cs, out.cs, res.cs if res is not None else 0,
+                    cv['act'], cv['slope'], ups, 0)
+            ops.append(dict(kind='conv', layer=i, xin=xin, out=out, res=res, res_layer=conv_res.get(i), ups=ups, desc=desc))
+        elif t == 'shortcut':
+            views[i] = view_for(i)
+            ops.append(dict(kind='add', layer=i, a=views[i - 1], b=views[_abs(i, int(d['from']))], out=views[i]))
+        elif t == 'upsample':
+            views[i] = view_for(i)
+            ops.append(dict(kind='upsample', layer=i, xin=views[i - 1], out=views[i], stride=int(d['stride'])))
+        elif t == 'maxpool':
+            views[i] = view_for(i)
+            ops.append(dict(kind='maxpool', layer=i, xin=views[i - 1], out=views[i], size=int(d['size']), stride=int(d['stride'])))
+        elif t == 'route':
+            if i in alias:
+                views[i] = views[alias[i]]
+            for src, off in copies.get(i, ()):
+                ops.append(dict(kind='copy', layer=i, xin=views[src], out=_slice(views[i], off, shp[src][0])))
+        elif t == 'yolo':
+            if pending_head is not None:
+                ops.append(dict(pending_head, layer=i))
+                pending_head = None                 # views[i] stays None: detect() materialises the head tensor on demand
+            else:
+                views[i] = views[i - 1]
+                ops.append(dict(kind='decode', layer=i, xin=views[i]))
+        elif t == 'reorg3d':
+            views[i] = views[i - 1]
+    return EvalPlan(shp, buffers, x, views, ops)
+
+
+# ------------------------------------------------------------------------------------------------ training
+def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, cin=3):
+    """TrainPlan(shapes, buffers, x, act, grd, forward, blocks, backward).  act[i] / grd[i]: activation / gradient view per layer
+    (same concat / slice structure).  forward: (kind, layer, record) with kind =
+      conv   a block: layer, desc, xin, xin_g (None for layer 0), y, dy, res, res_g, res_alias (the skip source's gradient IS dy),
+             bn, act, shape (C, H, W of the conv output z), recompute / one_pass (layer 0 without stored z / dz); with BatchNorm
+             z and dz are buffers of their own (unless recompute / one_pass), without they are y and dy
+      add    (a, b, y, a_g, b_g, dy)        up  (x, y, x_g, dy)        yolo  (head, head_g)
+    blocks: the conv records.  backward: (kind, layer, flags) in launch order (forward reversed); flags say which gradient views the
+    entry is the FIRST to write (it overwrites, later ones accumulate): conv (res_g, xin_g), add (a_g, b_g), up x_g; yolo: head index."""
+    n = len(defs)
+    shp = _shapes(defs, convs, cin, H, W)
+    for i, d in enumerate(defs):
+        if d['type'] == 'upsample' and int(d['stride']) != 2:
+            raise Refused("training path: only x2 upsampling")
+        if d['type'] == 'maxpool':
+            raise Refused("training path: maxpool graphs (yolov3-tiny) cannot train in the reference either "
+                          "(model/loss.py:248 hard-codes three heads)")
+    readers = _readers(defs)
+    fused_into, conv_res = {}, {}
+    for i, d in enumerate(defs):
+        if d['type'] == 'shortcut' and i > 0 and defs[i - 1]['type'] == 'convolutional' and readers[i - 1] == [i] \
+                and _abs(i, int(d['from'])) != i - 1 and convs[i - 1]['bn']:
+            fused_into[i] = i - 1
+            conv_res[i - 1] = _abs(i, int(d['from']))
+
+    buffers = []
+    x = _new(buffers, 8, H, W)
+
+    def new_pair(c, h, w):
+        return _new(buffers, c, h, w), _new(buffers, c, h, w)
+
+    act, grd = [None] * n, [None] * n
+    alias, concat = _routes(defs, shp)
+    home = {}
+    children = {}                        # concat gradient buffer -> the slices that live inside it
+    for i, srcs in concat.items():
+        act[i], grd[i] = new_pair(*shp[i])
+        for src, off in srcs:
+            if src in home or defs[src]['type'] not in ('convolutional', 'shortcut', 'upsample') or shp[src][0] % 8 or off % 8:
+                raise Refused("training path: route %d needs a copy (unsupported graph)" % i)
+            home[src] = (_slice(act[i], off, shp[src][0]), _slice(grd[i], off, shp[src][0]))
+            children.setdefault(grd[i], []).append(home[src][1])
+
+    def pair_for(i):
+        return home[i] if i in home else new_pair(*shp[i])
+
+    forward, blocks = [], []
+    for i, d in enumerate(defs):
+        t = d['type']
+        if i in fused_into:
+            act[i], grd[i] = act[fused_into[i]], grd[fused_into[i]]
+            continue
+        if t == 'convolutional':
+            cv = convs[i]
+            if cv.get('refuse'):
+                raise Refused(cv['refuse'])
+            xin, xin_g = (x, None) if i == 0 else (act[i - 1], grd[i - 1])
+            final = i + 1 if i in conv_res else i
+            y, dy = pair_for(final)
+            # residual chain: the gradient of this block's output and of its skip source are the same tensor
+            # (d(x + f(x)) passes dy to the skip branch unchanged) -- share ONE buffer instead of copying dy into the
+            # source's gradient: the block reads dy before the branch's dgrad accumulates onto it (launch order)
+            res_alias = False
+            if i in conv_res and final not in home:
+                rg = grd[conv_res[i]]
+                if rg is not None and rg[2:5] == dy[2:5] and rg.cs == rg.C:
+                    dy, res_alias = rg, True
+            act[i], grd[i] = y, dy
+            c, h, w = shp[i]
+            desc = (N, xin.H, xin.W, xin.C, c, cv['k'], cv['s'], cv['pad'], xin.cs, c, 0, 0, 0.0, 1, 0)
+            # layer 0 trains without its conv output: z0 (4 x the input, 27 MACs per value) is recomputed in the BatchNorm
+            # passes instead of being stored and re-read (include/ryolo.h: ryolo_conv0_*); its one-pass backward never materialises dz
+            recompute = bool(i == 0 and cv['bn'] and i not in conv_res and conv0_recompute
+                             and _query('ryolo_conv0_recompute_supported', desc))
+            blk = dict(layer=i, desc=desc, xin=xin, xin_g=xin_g, y=y, dy=dy, res=act[conv_res[i]] if i in conv_res else None,
+                       res_g=grd[conv_res[i]] if i in conv_res else None, res_alias=res_alias, bn=cv['bn'], act=cv['act'], shape=shp[i],
+                       recompute=recompute, one_pass=bool(recompute and xin_g is None and conv0_one_pass))
+            blocks.append(blk)
+            forward.append(('conv', i, blk))
+        elif t == 'shortcut':
+            a, b = i - 1, _abs(i, int(d['from']))
+            act[i], grd[i] = pair_for(i)
+            forward.append(('add', i, (act[a], act[b], act[i], grd[a], grd[b], grd[i])))
+        elif t == 'upsample':
+            act[i], grd[i] = pair_for(i)
+            forward.append(('up', i, (act[i - 1], act[i], grd[i - 1], grd[i])))
+        elif t == 'route':
+            if i in alias:
+                act[i], grd[i] = act[alias[i]], grd[alias[i]]
+        elif t == 'yolo':
+            act[i], grd[i] = act[i - 1], grd[i - 1]
+            forward.append(('yolo', i, (act[i], grd[i])))
+
+    # static accumulate flags of the backward pass (reverse order; the first contribution to a gradient view overwrites it)
+    init = set()
+
+    def first(g):
+        if g in init:
+            return False
+        init.add(g)
+        init.update(children.get(g, ()))      # writing a whole concat gradient initialises its channel slices
+        return True
+
+    heads = [i for kind, i, _ in forward if kind == 'yolo']
+    backward = []
+    for kind, i, pl in reversed(forward):
+        if kind == 'yolo':
+            first(pl[1])                                          # always the first (sole) writer of the head gradient
+            backward.append((kind, i, heads.index(i)))
+        elif kind == 'conv':
+            res_first = first(pl['res_g']) if (pl['res_g'] is not None and not pl['res_alias']) else None
+            backward.append((kind, i, (res_first, first(pl['xin_g']) if pl['xin_g'] is not None else None)))
+        elif kind == 'add':
+            backward.append((kind, i, (first(pl[3]), first(pl[4]))))
+        elif kind == 'up':
+            backward.append((kind, i, first(pl[2])))
+    return TrainPlan(shp, buffers, x, act, grd, forward, blocks, backward)
+
+
+def reduce_fusion_pairs(tp):
+    """The static half of the folded BatchNorm reduce: [(X, Y, rows)] block records of consecutive backward entries where X is a 1x1
+    conv whose data gradient writes the FINAL gradient of block Y's output (X consumed Y's output; in a residual chain X accumulates
+    into the chain's running gradient, which is Y's dy), that gradient is contiguous and Y has a stored-z BatchNorm.  Whether Y's
+    activation lets X's data gradient carry the reduce (ryolo_conv2d_dgrad_bnreduce, `rows` partial sums) is the caller's half."""
+    by = {b['layer']: b for b in tp.blocks}
+    pairs = []
+    for (k0, i0, _), (k1, i1, _) in zip(tp.backward[:-1], tp.backward[1:]):
+        if k0 != 'conv' or k1 != 'conv':
+            continue
+        x, y = by[i0], by[i1]
+        g, dy = x['xin_g'], y['dy']
+        if g is None or not y['bn'] or y['recompute'] or g != dy or dy[2:5] != y['shape'] or g.cs != g.C:
+            continue
+        rows = _query('ryolo_conv2d_dgrad_bnreduce_rows', x['desc'])
+        if rows > 0:
+            pairs.append((x, y, rows))
+    return pairs

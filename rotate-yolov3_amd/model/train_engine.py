@@ -30,7 +30,8 @@ import torch.nn as nn
 from .. import _lib
 from . import hip_ops as ops
 from . import hip_train_ops as tr
-from .engine import HipEngine, _abs
+from . import plan
+from .engine import HipEngine
 
 
 class _Fn(torch.autograd.Function):
@@ -66,87 +67,29 @@ class TrainEngine(object):
         self.device = device
         self.bs, cin, self.H, self.W = [int(v) for v in x_shape]
         defs, mods = model.module_defs, model.module_list
-        n = len(defs)
         self.defs, self.mods = defs, mods
 
-        # ---- shapes / readers / shortcut fusion / concat homes: same planning rules as the inference engine
-        shp = []
-        c, h, w = cin, self.H, self.W
-        for i, d in enumerate(defs):
-            t = d['type']
-            if t == 'convolutional':
-                conv = HipEngine._conv_of(mods[i])
-                k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-                c, h, w = conv.out_channels, (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
-            elif t == 'upsample':
-                s = int(d['stride'])
-                if s != 2:
-                    raise RuntimeError("training path: only x2 upsampling")
-                h, w = h * s, w * s
-            elif t == 'route':
-                ls = [_abs(i, int(v)) for v in d['layers'].split(',')]
-                c = sum(shp[l][0] for l in ls)
-                h, w = shp[ls[0]][1], shp[ls[0]][2]
-            elif t == 'maxpool':
-                raise RuntimeError("training path: maxpool graphs (yolov3-tiny) cannot train in the reference either "
-                                   "(model/loss.py:248 hard-codes three heads)")
-            shp.append((c, h, w))
-        self.shp = shp
-        readers = [[] for _ in range(n)]
-        for i, d in enumerate(defs):
-            if d['type'] == 'route':
-                for v in d['layers'].split(','):
-                    readers[_abs(i, int(v))].append(i)
-            else:
-                if i > 0:
-                    readers[i - 1].append(i)
-                if d['type'] == 'shortcut':
-                    readers[_abs(i, int(d['from']))].append(i)
-        fused_into, conv_res = {}, {}
-        for i, d in enumerate(defs):
-            if d['type'] == 'shortcut' and i > 0 and defs[i - 1]['type'] == 'convolutional' and readers[i - 1] == [i] \
-                    and _abs(i, int(d['from'])) != i - 1 and HipEngine._bn_of(mods[i - 1]) is not None:
-                fused_into[i] = i - 1
-                conv_res[i - 1] = _abs(i, int(d['from']))
+        # ---- the plan (model/plan.py): shapes, activation / gradient buffers (same concat / slice structure), blocks, who writes first.
+        # RYOLO_CONV0_RECOMPUTE=0 stores layer 0's conv output like any other, RYOLO_CONV0_ONE_PASS=0 keeps its dz and weight gradient
+        convs = {i: self._conv_attrs(mods[i]) for i, d in enumerate(defs) if d['type'] == 'convolutional'}
+        tp = self._tplan = plan.plan_train(defs, convs, self.bs, self.H, self.W,
+                                           conv0_recompute=os.environ.get('RYOLO_CONV0_RECOMPUTE', '1') != '0',
+                                           conv0_one_pass=os.environ.get('RYOLO_CONV0_ONE_PASS', '1') != '0', cin=cin)
+        self.shp = tp.shapes
 
-        def new_pair(c, h, w):
-            a = torch.empty((self.bs, h, w, c), dtype=torch.bfloat16, device=device)
-            return a, torch.empty_like(a)
+        def new_buf(c, h, w):
+            return torch.empty((self.bs, h, w, c), dtype=torch.bfloat16, device=device)
 
-        act = [None] * n     # activation view per layer
-        grd = [None] * n     # gradient view per layer (same structure)
-        home = {}
-        parent_of = {}
-        alias = {}
-        for i, d in enumerate(defs):
-            if d['type'] != 'route':
-                continue
-            ls = [_abs(i, int(v)) for v in d['layers'].split(',')]
-            if len(ls) == 1:
-                alias[i] = ls[0]
-                continue
-            c, h, w = shp[i]
-            a, g = new_pair(c, h, w)
-            act[i], grd[i] = a, g
-            off = 0
-            for l in ls:
-                src = l
-                while src in alias:
-                    src = alias[src]
-                if src in home or defs[src]['type'] not in ('convolutional', 'shortcut', 'upsample') or shp[src][0] % 8 or off % 8:
-                    raise RuntimeError("training path: route %d needs a copy (unsupported graph)" % i)
-                home[src] = (a[..., off:off + shp[src][0]], g[..., off:off + shp[src][0]])
-                parent_of[src] = (g.data_ptr(), tuple(g.shape), tuple(g.stride()))
-                off += shp[l][0]
+        bufs = [new_buf(*b) for b in tp.buffers]
+        tensors = {None: None}
 
-        def pair_for(i):
-            if i in home:
-                return home[i]
-            return new_pair(*shp[i])
+        def tv(v):
+            if v not in tensors:
+                tensors[v] = bufs[v.buf][..., v.off:v.off + v.C]
+            return tensors[v]
 
-        self.x_nhwc = torch.empty((self.bs, self.H, self.W, 8), dtype=torch.bfloat16, device=device)
-        cmax = max(ops.cpad(HipEngine._conv_of(m).out_channels) for d, m in zip(defs, mods) if d['type'] == 'convolutional')
-        cmax = max(cmax, max(ops.cpad(HipEngine._conv_of(m).in_channels) for d, m in zip(defs, mods) if d['type'] == 'convolutional'))
+        self.x_nhwc = tv(tp.x)
+        cmax = max(ops.cpad(max(c.out_channels, c.in_channels)) for c in (HipEngine._conv_of(mods[i]) for i in convs))
         self.ones = torch.ones(cmax, device=device)
         self.zeros = torch.zeros(cmax, device=device)
         self.stat_part = torch.zeros((tr.stat_rows(), 2, cmax), dtype=torch.float64, device=device)
@@ -155,95 +98,35 @@ class TrainEngine(object):
         self.static_grad = {}
         self.direct = False
         self.static_flat = None
-        init = set()                         # gradient views that already received their first contribution
-        children = {}                        # concat gradient buffer -> keys of the slices that live inside it
-
-        def key(t):
-            return (t.data_ptr(), tuple(t.shape), tuple(t.stride()))
-
-        def first(t):
-            k = key(t)
-            if k in init:
-                return False
-            init.add(k)
-            for ck in children.get(k, ()):      # writing a whole concat gradient initialises its channel slices
-                init.add(ck)
-            return True
-
-        for src, (a_s, g_s) in home.items():
-            children.setdefault(parent_of[src], []).append(key(g_s))
         wgrad_ws, bn_ws = 0, 0
-        plan = []    # (kind, layer, payload) in forward order
-        for i, d in enumerate(defs):
-            t = d['type']
-            if i in fused_into:
-                act[i], grd[i] = act[fused_into[i]], grd[fused_into[i]]
-                continue
-            if t == 'convolutional':
+        self.plan = fwd = []    # (kind, layer, payload) in forward order
+        for kind, i, rec in tp.forward:
+            if kind == 'conv':
                 conv = HipEngine._conv_of(mods[i])
                 bn = HipEngine._bn_of(mods[i])
-                actmod = None
-                is_mish = False
-                for s_ in mods[i]:
-                    if isinstance(s_, (nn.PReLU, nn.LeakyReLU)):
-                        actmod = s_
-                    elif type(s_).__name__ == 'Mish':
-                        is_mish = True
-                    elif not isinstance(s_, (nn.Conv2d, nn.BatchNorm2d)):
-                        # Swish etc. have no kernels here: refuse instead of training them as linear
-                        raise RuntimeError("activation %s has no HIP training kernels (use model.backend = 'torch')"
-                                           % type(s_).__name__)
-                xin = self.x_nhwc if i == 0 else act[i - 1]
-                xin_g = None if i == 0 else grd[i - 1]
-                k, s, pad = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-                final = i + 1 if i in conv_res else i
-                y, dy = pair_for(final)
-                # residual chain: the gradient of this block's output and of its skip source are the same tensor
-                # (d(x + f(x)) passes dy to the skip branch unchanged) -- share ONE buffer instead of copying dy into the
-                # source's gradient: the block reads dy before the branch's dgrad accumulates onto it (launch order)
-                res_alias = False
-                if i in conv_res and final not in home:
-                    rg = grd[conv_res[i]]
-                    if rg is not None and tuple(rg.shape) == tuple(dy.shape) and rg.is_contiguous():
-                        dy, res_alias = rg, True
-                act[i], grd[i] = y, dy
-                c, h, w = shp[i]
-                desc = tr.make_desc(xin, c, k, s, pad)
-                # layer 0 trains without its conv output: z0 (4 x the input, 27 MACs per value) is recomputed in the BatchNorm
-                # passes instead of being stored and re-read (include/ryolo.h: ryolo_conv0_*)
-                recompute = (i == 0 and bn is not None and i not in conv_res and tr.conv0_recompute_supported(desc)
-                             and os.environ.get('RYOLO_CONV0_RECOMPUTE', '1') != '0')
+                actmod = [s_ for s_ in mods[i] if isinstance(s_, (nn.PReLU, nn.LeakyReLU))]
+                xin, y, dy = tv(rec['xin']), tv(rec['y']), tv(rec['dy'])
+                c, h, w = rec['shape']
+                desc = ops.ConvDesc(*rec['desc'])
                 if bn is not None:
-                    z = None if recompute else torch.empty((self.bs, h, w, c), dtype=torch.bfloat16, device=device)
+                    z = None if rec['recompute'] else new_buf(c, h, w)
                     # (layer 0's one-pass backward never materialises dz: 1.5 GB at bs 64 / 608^2)
-                    one_pass = recompute and xin_g is None and os.environ.get('RYOLO_CONV0_ONE_PASS', '1') != '0'
-                    dz = None if one_pass else torch.empty((self.bs, h, w, c), dtype=torch.bfloat16, device=device)
+                    dz = None if rec['one_pass'] else new_buf(c, h, w)
                 else:
                     z, dz = y, dy            # linear bias conv: y IS z, dz IS dy
-                blk = dict(i=i, conv=conv, bn=bn, act=actmod, mish=is_mish, xin=xin, xin_g=xin_g, z=z, dz=dz, y=y, dy=dy, desc=desc,
-                           res=act[conv_res[i]] if i in conv_res else None,
-                           res_g=grd[conv_res[i]] if i in conv_res else None, res_alias=res_alias, cin_k=xin.shape[-1], k=k,
-                           s=s, pad=pad,
-                           npix=self.bs * h * w, C=c, recompute=recompute)
+                blk = dict(i=i, conv=conv, bn=bn, act=actmod[-1] if actmod else None, mish=any(type(s_).__name__ == 'Mish' for s_ in mods[i]),
+                           xin=xin, xin_g=tv(rec['xin_g']), z=z, dz=dz, y=y, dy=dy, desc=desc, res=tv(rec['res']), res_g=tv(rec['res_g']),
+                           res_alias=rec['res_alias'], cin_k=xin.shape[-1], k=desc.ksize, s=desc.stride, pad=desc.pad,
+                           npix=self.bs * h * w, C=c, recompute=rec['recompute'])
                 wgrad_ws = max(wgrad_ws, tr.wgrad_ws_bytes(desc))
                 bn_ws = max(bn_ws, tr.bn_bwd_ws_bytes(blk['npix'], c))
                 self.blocks.append(blk)
-                plan.append(('conv', i, blk))
-            elif t == 'shortcut':
-                a, b = i - 1, _abs(i, int(d['from']))
-                y, dy = pair_for(i)
-                act[i], grd[i] = y, dy
-                plan.append(('add', i, (act[a], act[b], y, grd[a], grd[b], dy)))
-            elif t == 'upsample':
-                y, dy = pair_for(i)
-                act[i], grd[i] = y, dy
-                plan.append(('up', i, (act[i - 1], y, grd[i - 1], dy)))
-            elif t == 'route':
-                if i in alias:
-                    act[i], grd[i] = act[alias[i]], grd[alias[i]]
-            elif t == 'yolo':
+                fwd.append(('conv', i, blk))
+            elif kind in ('add', 'up'):
+                fwd.append((kind, i, tuple(tv(v) for v in rec)))
+            elif kind == 'yolo':
                 m = mods[i]
-                c, h, w = shp[i]
+                c, h, w = tp.shapes[i]
                 anchors = m.anchors.to(device=device, dtype=torch.float32).contiguous()
                 pbuf = torch.empty((self.bs, m.na, h, w, model.nc + 6), dtype=torch.float32, device=device)
                 # training returns the raw heads only (models.py:189-194): the decoded rows are not written -- the p-only form
@@ -252,11 +135,9 @@ class TrainEngine(object):
                 if model.nc + 6 > 96 or m.na * (model.nc + 6) > 1024:
                     io = torch.empty((self.bs, m.na * h * w, model.nc + 6), dtype=torch.float32, device=device)
                 self.p.append(pbuf)
-                plan.append(('yolo', i, (act[i - 1], grd[i - 1], m, anchors, pbuf, io, h, w)))
-                act[i], grd[i] = act[i - 1], grd[i - 1]
-        self.plan = plan
+                fwd.append(('yolo', i, (tv(rec[0]), tv(rec[1]), m, anchors, pbuf, io, h, w)))
         # (head activation, head gradient) NHWC bf16 pairs in the order of self.p: the fused loss writes the gradients directly
-        self.head_pairs = [(pl[0], pl[1]) for kind, _, pl in plan if kind == 'yolo']
+        self.head_pairs = [(pl[0], pl[1]) for kind, _, pl in fwd if kind == 'yolo']
         self.fused_nhwc = False
         self.head_g_ready = False
         # (weight gradients on a second stream -- a parallel branch of the backward graphs -- were measured in rounds 2 and 5 and lost both
@@ -272,24 +153,19 @@ class TrainEngine(object):
         self._ws_w = None
         self.ws_b = torch.empty(max(bn_ws, 256), dtype=torch.uint8, device=device)
 
-        # ---- static accumulate flags for the backward pass (reverse order; first contribution overwrites)
-        self.bplan = []
-        for kind, i, pl in reversed(plan):
-            if kind == 'yolo':
-                head, head_g = pl[0], pl[1]
-                hidx = [k for k, q in enumerate(self.p) if q is pl[4]][0]
-                first(head_g)
-                self.bplan.append(('yolo', i, pl, hidx))               # always the first (sole) writer of the head grad
-            elif kind == 'conv':
-                blk = pl
-                res_first = first(blk['res_g']) if (blk['res_g'] is not None and not blk['res_alias']) else None
-                in_first = first(blk['xin_g']) if blk['xin_g'] is not None else None
-                self.bplan.append(('conv', i, blk, (res_first, in_first)))
-            elif kind == 'add':
-                a_g, b_g = pl[3], pl[4]
-                self.bplan.append(('add', i, pl, (first(a_g), first(b_g))))
-            elif kind == 'up':
-                self.bplan.append(('up', i, pl, first(pl[2])))
+        # ---- backward launch list: the forward entries reversed, each with its static accumulate flags (first contribution overwrites)
+        self.bplan = [(kind, i, pl, flags) for (kind, i, pl), (_, _, flags) in zip(reversed(fwd), tp.backward)]
+
+    @staticmethod
+    def _conv_attrs(m):
+        """what the planner reads of a `convolutional` block, from its modules; an activation without training kernels becomes the
+        planner's refusal when the walk reaches the layer (Swish etc.: refuse instead of training them as linear)"""
+        conv = HipEngine._conv_of(m)
+        other = [type(s_).__name__ for s_ in m if not isinstance(s_, (nn.Conv2d, nn.BatchNorm2d, nn.PReLU, nn.LeakyReLU))
+                 and type(s_).__name__ != 'Mish']
+        return dict(cout=conv.out_channels, k=conv.kernel_size[0], s=conv.stride[0], pad=conv.padding[0],
+                    bn=HipEngine._bn_of(m) is not None, act=None,
+                    refuse="activation %s has no HIP training kernels (use model.backend = 'torch')" % other[0] if other else None)
 
     # ------------------------------------------------------------------ parameter gradients
     # The backward kernels ACCUMULATE (+=) into fp32 buffers with STABLE addresses (hipGraph replays write to the same
@@ -696,20 +572,12 @@ class TrainEngine(object):
         self._red_planned = True
         if os.environ.get("RYOLO_BN_REDUCE_FUSION", "1") == "0":
             return
+        blk = {b['i']: b for b in self.blocks}
         pairs = []
-        for (k0, i0, x, f0), (k1, i1, y, f1) in zip(self.bplan[:-1], self.bplan[1:]):
-            if k0 != 'conv' or k1 != 'conv' or x['xin_g'] is None or y['bn'] is None or y.get('recompute'):
-                continue
-            if y.get('actcode') != 1 or y.get('slope') is None or y.get('stats') is None:
-                continue
-            g, dy, z = x['xin_g'], y['dy'], y['z']
-            if g.data_ptr() != dy.data_ptr() or g.shape != dy.shape or g.stride() != dy.stride() or z.shape != dy.shape:
-                continue
-            if g.stride(2) != g.shape[3]:
-                continue
-            rows = tr.dgrad_bnreduce_rows(x['desc'])
-            if rows > 0:
-                pairs.append((x, y, rows, g.shape[3]))
+        for xr, yr, rows in plan.reduce_fusion_pairs(self._tplan):          # the static half: geometry, BatchNorm, the kernel's rows
+            x, y = blk[xr['layer']], blk[yr['layer']]
+            if y.get('actcode') == 1 and y.get('slope') is not None and y.get('stats') is not None:
+                pairs.append((x, y, rows, x['xin_g'].shape[3]))
         if not pairs:
             return
         # one scratch for all pairs: a pair's rows are consumed by the very next entry of the launch list

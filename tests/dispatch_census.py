@@ -2,10 +2,8 @@
 shape-driven dispatch picks for it.  A helper module of the suite (not a conftest): tests/test_dispatch_census.py (CPU tier) and
 tests/test_dispatch_coverage_gpu.py (GPU tier) import it.
 
-The engines build their per-block descriptors while they allocate their activation buffers (model/engine.py HipEngine.__init__,
-model/train_engine.py TrainEngine.__init__), so the planning rules are mirrored here on buffer stand-ins (`_V`: channel stride,
-channel offset, identity) instead of tensors.  test_dispatch_coverage_gpu.py::test_census_matches_the_engines pins this mirror to
-the engines field by field.
+The plans come from the engines' own planner (rotate-yolov3_amd/model/plan.py), which needs no GPU; the cfg text stands in for the modules
+(`_conv`), and test_dispatch_coverage_gpu.py::test_census_matches_the_engines checks that adapter against the engines field by field.
 
 Call forms recorded per block:
   eval      ryolo_conv_kernel_choice(d, residual, 0) of the inference engine's single-conv launches
@@ -23,9 +21,9 @@ import ctypes as C
 import rotate_yolov3_amd  # noqa: F401  (installs the package under its importable name)
 from rotate_yolov3_amd import _lib
 from rotate_yolov3_amd.cfg import make_cfg
-from rotate_yolov3_amd.model import engine as _engine  # noqa: F401  (declares ryolo_conv_head_decode_supported)
 from rotate_yolov3_amd.model import hip_ops as ops
-from rotate_yolov3_amd.model import hip_train_ops as tr
+from rotate_yolov3_amd.model import hip_train_ops as tr  # noqa: F401  (declares the weight-gradient queries)
+from rotate_yolov3_amd.model import plan
 from rotate_yolov3_amd.utils.parse_config import parse_model_cfg_text, yolo_mask
 
 CONFIGS = (("darknet53", 1), ("darknet53", 2), ("darknet53", 15), ("tiny", 1), ("tiny", 80))
@@ -49,25 +47,7 @@ def mk_desc(t):
     return ops.ConvDesc(*t)
 
 
-class Refused(RuntimeError):
-    """the engine refuses this configuration (HipEngine raises RuntimeError at plan time)"""
-
-
-class _V(object):
-    """a buffer view: `base` identifies the allocation, `off` the channel offset inside it, `cs` the pixel stride"""
-    __slots__ = ("base", "off", "cs", "C", "H", "W")
-
-    def __init__(self, C_, H, W, base=None, off=0, cs=None):
-        self.base = base if base is not None else object()
-        self.off, self.C, self.H, self.W = off, C_, H, W
-        self.cs = cs if cs is not None else C_
-
-    def ptr(self):
-        return (id(self.base), self.off)
-
-
-def _abs(i, l):
-    return l if l > 0 else i + l
+Refused = plan.Refused      # the engines refuse this configuration at plan time
 
 
 def config_defs(kind, nc, H, W):
@@ -85,43 +65,12 @@ def _conv(d):
                 slope=0.1 if act == "leaky" else 0.0)
 
 
-def _shapes(defs, H, W, train):
-    shp = []
-    c, h, w = 3, H, W
-    for i, d in enumerate(defs):
-        t = d["type"]
-        if t == "convolutional":
-            cv = _conv(d)
-            c, h, w = cv["cout"], (h + 2 * cv["pad"] - cv["k"]) // cv["s"] + 1, (w + 2 * cv["pad"] - cv["k"]) // cv["s"] + 1
-        elif t == "maxpool":
-            if train:
-                raise ValueError("maxpool graphs do not train")
-            k, s = int(d["size"]), int(d["stride"])
-            if not (k == 2 and s == 1):
-                p = (k - 1) // 2
-                h, w = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
-        elif t == "upsample":
-            h, w = h * int(d["stride"]), w * int(d["stride"])
-        elif t == "route":
-            ls = [_abs(i, int(v)) for v in d["layers"].split(",")]
-            c = sum(shp[l][0] for l in ls)
-            h, w = shp[ls[0]][1], shp[ls[0]][2]
-        shp.append((c, h, w))
-    return shp
+def _convs(defs):
+    return {i: _conv(d) for i, d in enumerate(defs) if d["type"] == "convolutional"}
 
 
-def _readers(defs):
-    readers = [[] for _ in defs]
-    for i, d in enumerate(defs):
-        if d["type"] == "route":
-            for v in d["layers"].split(","):
-                readers[_abs(i, int(v))].append(i)
-        else:
-            if i > 0:
-                readers[i - 1].append(i)
-            if d["type"] == "shortcut":
-                readers[_abs(i, int(d["from"]))].append(i)
-    return readers
+def _yolos(defs):
+    return {i: (len(yolo_mask(d)), int(d["classes"]) + 6) for i, d in enumerate(defs) if d["type"] == "yolo"}
 
 
 def _L():
@@ -132,240 +81,44 @@ def _choice(t, residual, stats):
     return _L().ryolo_conv_kernel_choice(C.byref(mk_desc(t)), 1 if residual else 0, 1 if stats else 0)
 
 
-# ------------------------------------------------------------------------------------------------ eval engine mirror
+# ------------------------------------------------------------------------------------------------ the engines' conv launches
 def eval_blocks(defs, H, W, N):
-    """model/engine.py HipEngine.__init__ steps 1-4, conv launches only: [dict(form, layer, name, desc(s), ...)]"""
-    n = len(defs)
-    shp = _shapes(defs, H, W, False)
-    readers = _readers(defs)
-    fused_into, conv_res, conv_ups = {}, {}, {}
-    for i, d in enumerate(defs):
-        if i == 0 or defs[i - 1]["type"] != "convolutional" or readers[i - 1] != [i] or (i - 1) in fused_into.values():
-            continue
-        if d["type"] == "shortcut" and _abs(i, int(d["from"])) != i - 1:
-            fused_into[i] = i - 1
-            conv_res[i - 1] = _abs(i, int(d["from"]))
-        elif d["type"] == "upsample" and int(d["stride"]) == 2:
-            fused_into[i] = i - 1
-            conv_ups[i - 1] = 2
-    views, home, alias = [None] * n, {}, {}
-    for i, d in enumerate(defs):
-        if d["type"] != "route":
-            continue
-        ls = [_abs(i, int(v)) for v in d["layers"].split(",")]
-        if len(ls) == 1:
-            alias[i] = ls[0]
-            continue
-        c, h, w = shp[i]
-        buf = _V(c, h, w)
-        views[i] = buf
-        off = 0
-        for l in ls:
-            src = l
-            while src in alias:
-                src = alias[src]
-            if src not in home and defs[src]["type"] in ("convolutional", "shortcut", "upsample", "maxpool") and src < i \
-                    and shp[src][0] % 8 == 0 and off % 8 == 0:
-                home[src] = _V(shp[src][0], h, w, base=buf.base, off=off, cs=c)
-            off += shp[l][0]
-
-    def view_for(i):
-        return home[i] if i in home else _V(*shp[i])
-
-    x_nhwc = _V(8, H, W)
-    out_recs = []
-    pending = None
-    pending_head = None
-    for i, d in enumerate(defs):
-        t = d["type"]
-        if i in fused_into:
-            views[i] = views[fused_into[i]]
-            continue
-        if t == "convolutional":
-            cv = _conv(d)
-            xin = x_nhwc if i == 0 else views[i - 1]
-            cin_k = pending["cout"] if pending is not None else xin.C
-            final, res, ups = i, None, 1
-            if i in conv_res:
-                res, final = views[conv_res[i]], i + 1
-            if i in conv_ups:
-                ups, final = 2, i + 1
-            pair_first = pending is None and i + 1 < n and defs[i + 1]["type"] == "convolutional" and readers[i] == [i + 1] and \
-                i not in conv_res and i not in conv_ups and i not in home and (i + 1) not in conv_ups
-            head_cand = (not cv["bn"] and cv["k"] == 1 and cv["s"] == 1 and i + 1 < n and defs[i + 1]["type"] == "yolo" and
-                         readers[i] == [i + 1] and i not in home and i not in conv_res and i not in conv_ups)
-            out = None if (pair_first or head_cand) else view_for(final)
-            views[i] = out
-            if cv["cout"] % 8 or cin_k % 8:
-                raise Refused("conv %d: channel counts must be multiples of 8 for the HIP path" % i)     # engine.py: the same refusal
-            me = dict(layer=i, xin=xin, cin_k=cin_k, **cv)
-            if pending is not None:
-                first, pending = pending, None
-                a, b = _pair_descs(N, first, me, out.cs)
-                out_recs.append(dict(form="pair", layer=i, descs=(a, b), shortcut=res is not None, code=1,
-                                     name="conv_stem_pair<k%ds%d+k%ds%d%s>" % (first["k"], first["s"], cv["k"], cv["s"], "+res" if res is not None else "")))
-                continue
-            if (not cv["bn"] and cv["act"] == ops.ACT_LINEAR and cv["k"] == 1 and cv["s"] == 1 and res is None and ups == 1 and i + 1 < n and
-                    defs[i + 1]["type"] == "yolo" and readers[i] == [i + 1] and i not in home):
-                yd = defs[i + 1]
-                na, no = len(yolo_mask(yd)), int(yd["classes"]) + 6
-                ht = (N, xin.H, xin.W, xin.C, cv["cout"], 1, 1, 0, xin.cs, cv["cout"], 0, ops.ACT_LINEAR, 0.0, 1, 0)
-                if _L().ryolo_conv_head_decode_supported(C.byref(mk_desc(ht)), na, no):
-                    pending_head = dict(desc=ht, na=na, no=no, cin=xin.C)
-                    views[i] = None
-                    continue
-            if pair_first:
-                nx = _conv(defs[i + 1])
-                res_layer = conv_res.get(i + 1)
-                shortcut = res_layer is not None
-                if nx["bn"] and not (shortcut and views[res_layer] is not xin):
-                    a, b = _pair_descs(N, me, dict(nx, cin_k=cv["cout"]), None)
-                    if _L().ryolo_conv_pair_supported(C.byref(mk_desc(a)), C.byref(mk_desc(b)), 1 if shortcut else 0):
-                        pending = me
-                        continue
-            if out is None:
-                out = view_for(final)
-                views[i] = out
-            dt = (N, xin.H, xin.W, xin.C, cv["cout"], cv["k"], cv["s"], cv["pad"], xin.cs, out.cs, res.cs if res is not None else 0,
-                  cv["act"], cv["slope"], ups, 0)
-            code = _choice(dt, res is not None, False)
-            out_recs.append(dict(form="eval", layer=i, desc=dt, residual=res is not None, code=code,
-                                 name=ops.kernel_name_of(code, cv["k"], cv["s"], cin_k),
-                                 out_off=out.off, res_layer=conv_res.get(i)))
-        elif t in ("shortcut", "upsample", "maxpool"):
-            views[i] = view_for(i)
-        elif t == "route":
-            if i in alias:
-                views[i] = views[alias[i]]
-        elif t == "yolo":
-            if pending_head is not None:
-                hc, pending_head = pending_head, None
-                out_recs.append(dict(form="head", layer=i, desc=hc["desc"], na=hc["na"], no=hc["no"], code=1,
-                                     name="conv_pw<k1,K%d>+decode" % hc["cin"]))
-                views[i] = None
-                continue
-            views[i] = views[i - 1]
-        elif t == "reorg3d":
-            views[i] = views[i - 1]
-    return out_recs
+    """the conv launches of HipEngine's plan: [dict(form, layer, name, desc(s), ...)]"""
+    recs = []
+    for op in plan.plan_eval(defs, _convs(defs), _yolos(defs), N, H, W).ops:
+        if op["kind"] == "conv":
+            t = op["desc"]
+            code = _choice(t, op["res"] is not None, False)
+            recs.append(dict(form="eval", layer=op["layer"], desc=t, residual=op["res"] is not None, code=code,
+                             name=ops.kernel_name_of(code, t[5], t[6], t[3]), out_off=op["out"].off, res_layer=op["res_layer"]))
+        elif op["kind"] == "pair":
+            recs.append(dict(form="pair", layer=op["layer"], descs=op["descs"], shortcut=op["shortcut"], code=1, name=op["name"]))
+        elif op["kind"] == "head":
+            recs.append(dict(form="head", layer=op["layer"], desc=op["desc"], na=op["na"], no=op["no"], code=1, name=op["name"]))
+    return recs
 
 
-def _pair_descs(N, first, second, out_cs):
-    """hip_ops.pair_descs on a buffer stand-in"""
-    x = first["xin"]
-    a = (N, x.H, x.W, x.C, first["cout"], first["k"], first["s"], first["pad"], x.cs, first["cout"], 0, first["act"], first["slope"], 1, 0)
-    h1 = (x.H + 2 * first["pad"] - first["k"]) // first["s"] + 1
-    w1 = (x.W + 2 * first["pad"] - first["k"]) // first["s"] + 1
-    b = (N, h1, w1, first["cout"], second["cout"], second["k"], second["s"], second["pad"], first["cout"], out_cs or second["cout"], 0,
-         second["act"], second["slope"], 1, 0)
-    return a, b
-
-
-# ------------------------------------------------------------------------------------------------ train engine mirror
 def train_blocks(defs, H, W, N):
-    """model/train_engine.py TrainEngine.__init__ + _plan_reduce_fusion: per conv block its descriptor and the four call forms"""
-    n = len(defs)
-    shp = _shapes(defs, H, W, True)
-    readers = _readers(defs)
-    fused_into, conv_res = {}, {}
-    for i, d in enumerate(defs):
-        if d["type"] == "shortcut" and i > 0 and defs[i - 1]["type"] == "convolutional" and readers[i - 1] == [i] \
-                and _abs(i, int(d["from"])) != i - 1 and _conv(defs[i - 1])["bn"]:
-            fused_into[i] = i - 1
-            conv_res[i - 1] = _abs(i, int(d["from"]))
-
-    def new_pair(c, h, w):
-        return _V(c, h, w), _V(c, h, w)
-
-    act, grd = [None] * n, [None] * n
-    home, alias = {}, {}
-    for i, d in enumerate(defs):
-        if d["type"] != "route":
-            continue
-        ls = [_abs(i, int(v)) for v in d["layers"].split(",")]
-        if len(ls) == 1:
-            alias[i] = ls[0]
-            continue
-        c, h, w = shp[i]
-        a, g = new_pair(c, h, w)
-        act[i], grd[i] = a, g
-        off = 0
-        for l in ls:
-            src = l
-            while src in alias:
-                src = alias[src]
-            home[src] = (_V(shp[src][0], h, w, base=a.base, off=off, cs=c), _V(shp[src][0], h, w, base=g.base, off=off, cs=c))
-            off += shp[l][0]
-
-    def pair_for(i):
-        return home[i] if i in home else new_pair(*shp[i])
-
-    x_nhwc = _V(8, H, W)
-    plan, blocks = [], []
-    for i, d in enumerate(defs):
-        t = d["type"]
-        if i in fused_into:
-            act[i], grd[i] = act[fused_into[i]], grd[fused_into[i]]
-            continue
-        if t == "convolutional":
-            cv = _conv(d)
-            xin = x_nhwc if i == 0 else act[i - 1]
-            xin_g = None if i == 0 else grd[i - 1]
-            final = i + 1 if i in conv_res else i
-            y, dy = pair_for(final)
-            if i in conv_res and final not in home:
-                rg = grd[conv_res[i]]
-                if rg is not None and (rg.C, rg.H, rg.W) == (dy.C, dy.H, dy.W) and rg.cs == rg.C:
-                    dy = rg
-            act[i], grd[i] = y, dy
-            c, h, w = shp[i]
-            dt = (N, xin.H, xin.W, xin.C, c, cv["k"], cv["s"], cv["pad"], xin.cs, c, 0, 0, 0.0, 1, 0)
-            recompute = i == 0 and cv["bn"] and i not in conv_res and bool(_L().ryolo_conv0_recompute_supported(C.byref(mk_desc(dt))))
-            one_pass = recompute and xin_g is None
-            blk = dict(layer=i, desc=dt, bn=cv["bn"], prelu=cv["act"] == ops.ACT_LEAKY, recompute=recompute, one_pass=one_pass,
-                       xin_g=xin_g, dy=dy, z_shape=(c, h, w), cin_real=3 if i == 0 else xin.C, residual=i in conv_res)
-            blocks.append(blk)
-            plan.append(("conv", blk))
-        elif t == "shortcut":
-            act[i], grd[i] = pair_for(i)
-            plan.append(("add", None))
-        elif t == "upsample":
-            act[i], grd[i] = pair_for(i)
-            plan.append(("up", None))
-        elif t == "route":
-            if i in alias:
-                act[i], grd[i] = act[alias[i]], grd[alias[i]]
-        elif t == "yolo":
-            act[i], grd[i] = act[i - 1], grd[i - 1]
-            plan.append(("yolo", None))
-    # _plan_reduce_fusion: consecutive backward entries (X, Y) = (plan[k + 1], plan[k])
-    bplan = list(reversed(plan))
-    for (k0, x), (k1, y) in zip(bplan[:-1], bplan[1:]):
-        if k0 != "conv" or k1 != "conv" or x["xin_g"] is None or not y["bn"] or y["recompute"] or not y["prelu"]:
-            continue
-        g, dy = x["xin_g"], y["dy"]
-        if g.ptr() != dy.ptr() or (g.C, g.H, g.W) != (dy.C, dy.H, dy.W) or g.cs != dy.cs or y["z_shape"] != (dy.C, dy.H, dy.W):
-            continue
-        if g.cs != g.C:
-            continue
-        if tr.dgrad_bnreduce_rows(mk_desc(x["desc"])) > 0:
-            x["bnred"] = True
+    """TrainEngine's plan + the folded BatchNorm reduce: per conv block its descriptor and the four call forms"""
+    tp = plan.plan_train(defs, _convs(defs), N, H, W)
+    # the engine's run-time half of the fold: Y is a BatchNorm + PReLU / leaky block
+    bnred = set(x["layer"] for x, y, rows in plan.reduce_fusion_pairs(tp) if y["act"] == ops.ACT_LEAKY)
     recs = []
     L = _L()
-    for b in blocks:
+    for b in tp.blocks:
         dt = b["desc"]
         d = mk_desc(dt)
         code = L.ryolo_conv_kernel_choice(C.byref(d), 0, 1 if b["bn"] else 0)
         recs.append(dict(form="train", layer=b["layer"], desc=dt, code=code, stats=b["bn"], recompute=b["recompute"],
                          name=ops.kernel_name_of(code, dt[5], dt[6], dt[3])))
         if b["xin_g"] is not None:
-            red = bool(b.get("bnred"))
+            red = b["layer"] in bnred
             code = L.ryolo_conv_dgrad_kernel_choice(C.byref(d), 1 if red else 0)
             recs.append(dict(form="dgrad", layer=b["layer"], desc=dt, code=code, bnred=red,
                              name=ops.kernel_name_of(code, dt[5], 1, dt[4])))
         if not (b["bn"] and b["recompute"] and b["one_pass"]):
             code = L.ryolo_conv_wgrad_kernel_choice(C.byref(d))
-            recs.append(dict(form="wgrad", layer=b["layer"], desc=dt, code=code, cin_real=b["cin_real"], splits=wgrad_splits(dt, code)))
+            recs.append(dict(form="wgrad", layer=b["layer"], desc=dt, code=code, cin_real=3 if b["layer"] == 0 else dt[3], splits=wgrad_splits(dt, code)))
     return recs
 
 

@@ -33,7 +33,7 @@ GUARD = 4096
 @pytest.fixture(scope="module")
 def env(cuda_dev):
     from rotate_yolov3_amd import _lib
-    from rotate_yolov3_amd.model import hip_ops, hip_train_ops
+    from rotate_yolov3_amd.model import engine, hip_ops, hip_train_ops  # noqa: F401  (engine declares ryolo_conv_head_decode, which the head cases launch)
     torch.backends.cuda.matmul.allow_tf32 = False
     torch.backends.cudnn.allow_tf32 = False
     cus = torch.cuda.get_device_properties(cuda_dev).multi_processor_count
@@ -364,8 +364,9 @@ def test_every_census_class_against_aten(env, cuda_dev):
 
 
 def test_census_matches_the_engines(env, cuda_dev):
-    """the census's mirror of the engines' planning, pinned at 608^2 / bs 4: every training block's descriptor equals the engine's
-    blk['desc'] field by field, and the inference engine's conv launches (layer, kernel name) equal the census's"""
+    """the census plans from the cfg text, the engines from the modules (same planner, model/plan.py), pinned at 608^2 / bs 4: every training
+    block's descriptor equals the engine's blk['desc'] field by field, the inference engine's conv launches (layer, kernel name) equal
+    the census's, and the tensors the engine materialised have the plan's geometry"""
     from rotate_yolov3_amd.cfg import make_cfg
     from rotate_yolov3_amd.model.engine import HipEngine
     from rotate_yolov3_amd.model.models import Darknet

@@ -32,7 +32,8 @@ extern "C" {
 #define RYOLO_RNMS_MAX_BOXES 262144
 
 const char *ryolo_strerror(int code);
-/* ABI version; bumped when a signature changes. */
+/* ABI version; bumped when a signature or a contract changes.  3: ryolo_rnms_workspace_bytes grew (the split scan's state words) and
+ * ryolo_set_tuning was added since 2; ryolo_rnms on a capturing stream runs unsplit. */
 int ryolo_abi_version(void);
 /* "RYOLO_BUILD_ID=" + 16 hex digits: a hash of the library's sources, headers and compiler flags (__graft_entry__.source_id()). */
 const char *ryolo_build_id(void);
@@ -62,6 +63,12 @@ int ryolo_set_tuning(const char *name, const char *value);
  * Calls of more than 20 416 boxes run part of their work on a second, library-owned stream (the scan of the first block rows beside
  * the IoU kernel of the last ones); HIP events order it inside the call's position on `stream` -- for the caller the call is still
  * "enqueued on `stream`": everything enqueued on `stream` before it is visible to it, everything after it sees its results.
+ * Stream rules of that split:
+ *   - a call on a CAPTURING stream runs unsplit (asked with hipStreamIsCapturing on every call): a captured ryolo_rnms is a linear
+ *     chain of launches on `stream` alone, whatever was called before it, and replays on whatever `dets` holds by then;
+ *   - concurrent eager calls (several host threads, several streams) are serialised on one library stream per device -- the one
+ *     mutex-guarded stream + two events of the calling thread's current device; each call needs its own workspace, keep_out and num_keep;
+ *   - if an event call fails, the rest of the work is enqueued on `stream` in order and the call returns RYOLO_ELAUNCH.
  */
 size_t ryolo_rnms_workspace_bytes(int n);
 int ryolo_rnms(const float *dets, int n, int row_stride, float thr, int64_t *keep_out, int32_t *num_keep,

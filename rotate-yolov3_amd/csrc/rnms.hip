@@ -936,19 +936,26 @@ struct SidePool {
 };
 static std::mutex g_side_mutex;
 static SidePool g_side[16];
-// the second stream + two events of the current device, created on first use (not while `stream` is being captured into a graph:
-// stream / event creation is illegal there -- such a call runs unsplit until a call outside a capture has created them)
-static SidePool *side_pool(hipStream_t stream) {
+// the second stream + two events of the calling thread's current device, created on first use.  The caller holds g_side_mutex and has
+// established that its stream is not being captured (stream / event creation is illegal during a capture; ryolo_rnms asks on every call).
+// A pool that could only be created in part is destroyed again: no stream or event is left behind, and the device stays unsplit.
+static SidePool *side_pool() {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return nullptr; }
     SidePool &sp = g_side[dev];
     if (sp.state == 0) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return nullptr; }
         const bool ok = hipStreamCreateWithFlags(&sp.s, hipStreamNonBlocking) == hipSuccess &&
                         hipEventCreateWithFlags(&sp.a, hipEventDisableTiming) == hipSuccess &&
                         hipEventCreateWithFlags(&sp.b, hipEventDisableTiming) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
+        if (!ok) {
+            (void)hipGetLastError();
+            if (sp.b) (void)hipEventDestroy(sp.b);
+            if (sp.a) (void)hipEventDestroy(sp.a);
+            if (sp.s) (void)hipStreamDestroy(sp.s);
+            sp.s = nullptr;
+            sp.a = sp.b = nullptr;
+            (void)hipGetLastError();
+        }
         sp.state = ok ? 1 : -1;
     }
     return sp.state == 1 ? &sp : nullptr;
@@ -969,7 +976,7 @@ const char *ryolo_strerror(int code) {
     }
 }
 
-int ryolo_abi_version(void) { return 2; }
+int ryolo_abi_version(void) { return 3; }      // 3: the NMS workspace sizes grew and ryolo_set_tuning was added since 2; a capturing stream runs ryolo_rnms unsplit
 
 void ryolo_rnms_count_pairs(uint64_t *device_counter) { g_pair_counter = (unsigned long long *)device_counter; }
 
@@ -1019,21 +1026,43 @@ int ryolo_rnms(const float *dets, int n, int row_stride, float thr, int64_t *kee
         if (e && e[0] == '0') split = false;
     }
     if (split) {
-        std::lock_guard<std::mutex> lock(g_side_mutex);                // the pool's events are shared by the host threads of a process
-        SidePool *sp = side_pool(stream);
+        // Asked on EVERY call: a call on a capturing stream runs unsplit, so a captured NMS is one linear chain of launches on `stream`
+        // (no fork onto the process-wide second stream, which other calls use at the same time; no parallel branches to replay).
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); split = false; }
+        else if (cs != hipStreamCaptureStatusNone) split = false;
+    }
+    if (split) {
+        // One pool per device for all host threads: the lock covers the enqueue only.  hipStreamWaitEvent binds to the event's record at
+        // the time of the call, so the next caller may re-record `a` / `b` as soon as this one has left; concurrent large calls are
+        // serialised on the one second stream, nothing else.
+        std::lock_guard<std::mutex> lock(g_side_mutex);
+        SidePool *sp = side_pool();
         if (sp) {
             const int NP = (W + PANEL - 1) / PANEL, pe = NP * 3 / 5, k = pe * PANEL;
             // the caller's stream: rows [0, k), then the first panel steps; the second stream: rows [k, W) as soon as the first launch is done.
             // (The other way round -- scan beside a mask launch already resident -- the scan's one 1024-thread workgroup found no CU with 16
             //  free wave slots and 100 KiB of LDS until the mask launch had drained: no overlap at all.  Here the scan is the next packet of
             //  the stream that just finished, the mask launch waits for an event on another queue: the scan is placed first.)
+            // Every event call is checked BEFORE the work that depends on it is enqueued.  When one fails, the rows [k, W) go onto `stream`
+            // itself -- stream order then stands in for the event -- the remaining panel steps follow, and the call reports RYOLO_ELAUNCH.
             launch_mask(n, thr, P0, P1, AUX, tiles, summ, W, 1, nullptr, 0ll, stream, 0, k);
-            bool ok = hipEventRecord(sp->a, stream) == hipSuccess;
+            const bool recorded = hipEventRecord(sp->a, stream) == hipSuccess;
             hipLaunchKernelGGL(rnms_scan_kernel, dim3(1), dim3(SCAN_THREADS), smem, stream, n, tiles, summ, order, flags,
-                               keep_out, num_keep, (const int32_t *)nullptr, 0ll, 0, pe, state);
-            ok = ok && hipStreamWaitEvent(sp->s, sp->a, 0) == hipSuccess;
-            launch_mask(n, thr, P0, P1, AUX, tiles, summ, W, 1, nullptr, 0ll, sp->s, k, W);
-            ok = ok && hipEventRecord(sp->b, sp->s) == hipSuccess && hipStreamWaitEvent(stream, sp->b, 0) == hipSuccess;
+                               keep_out, num_keep, (const int32_t *)nullptr, 0ll, 0, pe, state);        // needs rows [0, k) only: stream order
+            bool ok = recorded && hipStreamWaitEvent(sp->s, sp->a, 0) == hipSuccess;
+            if (ok) {
+                launch_mask(n, thr, P0, P1, AUX, tiles, summ, W, 1, nullptr, 0ll, sp->s, k, W);
+                ok = hipEventRecord(sp->b, sp->s) == hipSuccess && hipStreamWaitEvent(stream, sp->b, 0) == hipSuccess;
+            }
+            if (!ok) {
+                // not forked, or forked and not joined: in the second case the launch on the second stream writes the same tile words
+                // and summaries as this one (each is stored once, whole, a function of the boxes alone), so whichever lands last the scan reads
+                // them.  That launch is ordered with nothing afterwards: RYOLO_ELAUNCH also means "synchronise the device before the workspace
+                // is used again".
+                (void)hipGetLastError();
+                launch_mask(n, thr, P0, P1, AUX, tiles, summ, W, 1, nullptr, 0ll, stream, k, W);
+            }
             hipLaunchKernelGGL(rnms_scan_kernel, dim3(1), dim3(SCAN_THREADS), smem, stream, n, tiles, summ, order, flags,
                                keep_out, num_keep, (const int32_t *)nullptr, 0ll, pe, -1, state);
             return ok ? check_launch() : RYOLO_ELAUNCH;

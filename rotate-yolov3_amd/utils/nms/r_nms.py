@@ -13,16 +13,14 @@ import torch
 
 from ... import _lib
 
-_workspaces = {}
-
 
 def _workspace(device, nbytes):
-    key = (device.type, device.index)
-    ws = _workspaces.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(int(nbytes * 1.25) if ws is not None else nbytes, dtype=torch.uint8, device=device)
-        _workspaces[key] = ws
-    return ws
+    """Scratch of ONE call, taken from torch's caching allocator on the current stream of `device` (the caller has made it the current
+    device).  The allocator is stream-aware: the block returns to its pool when the tensor dies and is handed out again only to
+    allocations on the same stream, behind this call in stream order -- so calls in flight on different streams or host threads never
+    share scratch, and nothing a running call uses is ever dropped by a larger request elsewhere.  While the stream is being captured
+    the block comes from the graph's private pool and lives as long as the graph.  A cache hit costs no host synchronisation."""
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
 
 
 def r_nms(dets, threshold):

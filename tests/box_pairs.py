@@ -1,4 +1,5 @@
-"""Shared test data / independent checker for the evaluation-path rotated IoU (tests/test_oracle_poly_iou.py, tests/test_skewiou_gpu.py)."""
+"""Shared test data / independent checker for the evaluation-path rotated IoU (tests/test_oracle_poly_iou.py, tests/test_skewiou_gpu.py)
+and the clustered NMS boxes of the split-scan tests (tests/test_rnms_gpu.py, tests/test_stream_contract_gpu.py)."""
 import math
 
 import numpy as np
@@ -79,3 +80,18 @@ def qhull_iou(b1, b2, get_rotated_coors, shoelace):
     if res.success and res.x[2] > 1e-9:
         inter = float(ConvexHull(HalfspaceIntersection(hs, res.x[:2]).intersections).volume)
     return inter / (b1[2] * b1[3] + b2[2] * b2[3] - inter)
+
+
+def clustered_boxes(n, rng, bg_seed, clusters=30, members=100, extent=700.0, jitter=1.5):
+    """[n, 6] NMS boxes for the split scan of ryolo_rnms: n - clusters * members background boxes (oracle.riou.random_boxes, seed bg_seed)
+    plus `clusters` clusters of `members` near-duplicates of a background box each, the members' scores uniform over the whole score
+    order -- so boxes kept early (the first mask launch / first scan launch of a split call) suppress boxes that come late (the second):
+    the state handed from one piece to the other matters.  Rows in random order; every draw comes from `rng`, in a fixed sequence."""
+    from oracle import riou
+    bg = riou.random_boxes(n - clusters * members, seed=bg_seed, extent=extent)
+    centers = bg[rng.choice(len(bg), clusters, replace=False)]
+    cl = np.repeat(centers, members, axis=0)
+    cl[:, 0:2] += rng.normal(0, jitter, (len(cl), 2)).astype(np.float32)
+    cl[:, 5] = rng.uniform(0, 1, len(cl)).astype(np.float32)          # cluster members spread over the whole score order
+    d = np.concatenate([bg, cl], 0).astype(np.float32)
+    return d[rng.permutation(len(d))]

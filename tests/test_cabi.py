@@ -78,6 +78,32 @@ def test_tuning_switches_are_a_closed_set_and_the_library_reads_no_environment_o
     assert len(calls) == 1 and "TUNE_NAMES" in calls[0], calls
 
 
+def test_rnms_asks_for_a_capture_on_every_call_not_only_when_it_creates_its_side_stream():
+    """include/ryolo.h: a ryolo_rnms call on a capturing stream runs unsplit.  The question (hipStreamIsCapturing on the caller's stream)
+    has to be asked by ryolo_rnms itself on every call that could split, before it touches the pool of the second stream -- not inside
+    the pool's create-on-first-use branch (`state == 0`), where it is only asked until some eager call has created the pool
+    (tests/test_stream_contract_gpu.py runs the sequence on a GPU)."""
+    src = open(os.path.join(ROOT, "rotate-yolov3_amd", "csrc", "rnms.hip")).read()
+    src = re.sub(r"//[^\n]*", "", src)
+
+    def body(header_re):
+        m = re.search(header_re, src)
+        assert m, header_re
+        depth, i = 1, m.end()
+        while depth:
+            depth += {"{": 1, "}": -1}.get(src[i], 0)
+            i += 1
+        return src[m.end():i - 1]
+
+    fn = body(r"\bint\s+ryolo_rnms\s*\([^)]*\)\s*\{")
+    ask = re.search(r"\bhipStreamIsCapturing\s*\(\s*stream\s*,", fn)
+    pool = re.search(r"\bside_pool\s*\(", fn)
+    assert ask and pool and ask.start() < pool.start()
+    assert not re.search(r"state\s*==\s*0", fn[:ask.start()])
+    # and the pool itself creates streams / events without asking: the answer of one call must not stand for the next
+    assert not re.search(r"hipStreamIsCapturing", body(r"\bSidePool\s*\*\s*side_pool\s*\([^)]*\)\s*\{"))
+
+
 def test_product_does_not_import_oracle():
     pkg = os.path.join(ROOT, "rotate-yolov3_amd")
     for dirpath, _, files in os.walk(pkg):

@@ -29,10 +29,6 @@
 
 #include "conv_common.h"
 
-namespace ryolo_detail {
-thread_local int *g_conv_choice = nullptr;      // see conv_common.h
-}
-
 using namespace ryolo_detail;
 
 namespace {
@@ -1219,21 +1215,25 @@ __global__ void conv0_bwd_finalize_kernel(double *__restrict__ part, const float
 
 template <int ACT>
 static int launch_c8_bwd(ConvParams &p, int gpw, unsigned nblk, const C8Bwd &bw, int mode, hipStream_t stream) {
-    if (mode == 2) hipLaunchKernelGGL((conv3x3_c8_direct_kernel<false, ACT, 2>), dim3(nblk), dim3(256), 0, stream, p, gpw, bw);
-    else hipLaunchKernelGGL((conv3x3_c8_direct_kernel<false, ACT, 3>), dim3(nblk), dim3(256), 0, stream, p, gpw, bw);
-    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+    if (mode == 0) return launch_kernel<conv3x3_c8_direct_kernel<false, ACT, 0>>(dim3(nblk), dim3(256), 0, stream, p, gpw, bw);
+    if (mode == 2) return launch_kernel<conv3x3_c8_direct_kernel<false, ACT, 2>>(dim3(nblk), dim3(256), 0, stream, p, gpw, bw);
+    return launch_kernel<conv3x3_c8_direct_kernel<false, ACT, 3>>(dim3(nblk), dim3(256), 0, stream, p, gpw, bw);
+}
+// mode 0: the training forward (round_z), 2 / 3: the two backward passes
+static int launch_c8_mode(int act, ConvParams &p, int gpw, unsigned nblk, const C8Bwd &bw, int mode, hipStream_t stream) {
+    if (act == RYOLO_ACT_LEAKY) return launch_c8_bwd<RYOLO_ACT_LEAKY>(p, gpw, nblk, bw, mode, stream);
+    if (act == RYOLO_ACT_MISH) return launch_c8_bwd<RYOLO_ACT_MISH>(p, gpw, nblk, bw, mode, stream);
+    return launch_c8_bwd<RYOLO_ACT_LINEAR>(p, gpw, nblk, bw, mode, stream);
 }
 
 template <bool STATS>
 int launch_c8_direct(ConvParams &p, int gpw, unsigned nblk, hipStream_t stream) {
-    if (STATS && p.y == nullptr) {        // statistics only (layer 0 of the training engine: z is recomputed, never stored)
-        hipLaunchKernelGGL((conv3x3_c8_direct_kernel<true, RYOLO_ACT_LINEAR, 1>), dim3(nblk), dim3(256), 0, stream, p, gpw, C8Bwd());
-        return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
-    }
-    if (p.act == RYOLO_ACT_LEAKY) hipLaunchKernelGGL((conv3x3_c8_direct_kernel<STATS, RYOLO_ACT_LEAKY>), dim3(nblk), dim3(256), 0, stream, p, gpw);
-    else if (p.act == RYOLO_ACT_MISH) hipLaunchKernelGGL((conv3x3_c8_direct_kernel<STATS, RYOLO_ACT_MISH>), dim3(nblk), dim3(256), 0, stream, p, gpw);
-    else hipLaunchKernelGGL((conv3x3_c8_direct_kernel<STATS, RYOLO_ACT_LINEAR>), dim3(nblk), dim3(256), 0, stream, p, gpw);
-    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+    const dim3 g(nblk), b(256);
+    if (STATS && p.y == nullptr)          // statistics only (layer 0 of the training engine: z is recomputed, never stored)
+        return launch_kernel<conv3x3_c8_direct_kernel<true, RYOLO_ACT_LINEAR, 1>>(g, b, 0, stream, p, gpw, C8Bwd());
+    if (p.act == RYOLO_ACT_LEAKY) return launch_kernel<conv3x3_c8_direct_kernel<STATS, RYOLO_ACT_LEAKY>>(g, b, 0, stream, p, gpw, C8Bwd());
+    if (p.act == RYOLO_ACT_MISH) return launch_kernel<conv3x3_c8_direct_kernel<STATS, RYOLO_ACT_MISH>>(g, b, 0, stream, p, gpw, C8Bwd());
+    return launch_kernel<conv3x3_c8_direct_kernel<STATS, RYOLO_ACT_LINEAR>>(g, b, 0, stream, p, gpw, C8Bwd());
 }
 
 __global__ void pack_weights_kernel(const float *__restrict__ w, int Cout, int Cin, int KS, int Cin_pad, int Kpad,
@@ -1284,18 +1284,6 @@ __global__ void nhwc_bf16_to_nchw_f32_kernel(const __bf16 *__restrict__ x, int N
     }
 }
 
-inline int ilog2_exact(int v) {
-    int l = 0;
-    while ((1 << l) < v) l++;
-    return (1 << l) == v ? l : -1;
-}
-
-// set by ryolo_conv2d_dgrad_bnreduce around its dispatch: the launch must be the persistent 1x1 kernel's BNRED instantiation
-static thread_local const BnRed *g_bnred = nullptr;
-static thread_local int g_bnred_mode = 0;        // bnreduce_plan's choice (the partial rows are sized for that launch): 1 conv_pw.hip's MODE 3, 2 the
-                                                 // persistent 2x2 tile (one row per workgroup), 3 a one-tile-per-workgroup tile (one row per pixel tile),
-                                                 // 4 conv_mq.hip's 128-channel tiles (one row per workgroup)
-
 // tile code of a (BM, BN, WGM, WGN, NSTAGE) instantiation as ryolo_conv_desc::tile / RYOLO_CONV_KERNEL_IGEMM + code name it
 template <int BM, int BN, int WGM, int WGN, int NSTAGE>
 constexpr int igemm_tile_code() {
@@ -1310,106 +1298,57 @@ constexpr bool igemm_bnred_inst() {
 }
 
 template <int KS, int BM, int BN, int WGM, int WGN, int NSTAGE, bool FAST, bool GEN>
-int launch_variant_impl(ConvParams &p, hipStream_t stream) {
-    if (g_bnred) {
+int launch_variant_impl(ConvParams &p, const ConvLaunch &lc) {
+    constexpr size_t smem = NSTAGE * (BM + BN) * BK * 2;
+    constexpr int code = RYOLO_CONV_KERNEL_IGEMM + igemm_tile_code<BM, BN, WGM, WGN, NSTAGE>();
+    p.nt = (p.Cout + BN - 1) / BN;
+    const dim3 grid((unsigned)((p.M + BM - 1) / BM * p.nt)), block(WGM * WGN * 64);
+    if (lc.bnred) {
         if constexpr (FAST && !GEN && igemm_bnred_inst<KS, BM, BN, WGM, WGN, NSTAGE>()) {
-            if (g_bnred_mode != 3 || p.stat_part || p.ups != 1 || p.os != 1) return RYOLO_EINVAL;
-            RYOLO_CONV_DRY_RUN((RYOLO_CONV_KERNEL_IGEMM + igemm_tile_code<BM, BN, WGM, WGN, NSTAGE>()));
-            constexpr size_t smem_bn = NSTAGE * (BM + BN) * BK * 2;
-            static bool attr_bn = false;
-            auto kbn = conv_igemm_kernel<KS, BM, BN, WGM, WGN, NSTAGE, true, false, true>;
-            if (!attr_bn) {
-                if (smem_bn > 64 * 1024 &&
-                    hipFuncSetAttribute((const void *)kbn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_bn) != hipSuccess)
-                    return RYOLO_ELAUNCH;
-                attr_bn = true;
-            }
-            const int mt = (p.M + BM - 1) / BM;
-            p.nt = (p.Cout + BN - 1) / BN;
-            hipLaunchKernelGGL(kbn, dim3((unsigned)(mt * p.nt)), dim3(WGM * WGN * 64), smem_bn, stream, p, *g_bnred);
-            return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+            if (lc.bnred_mode != 3 || p.stat_part || p.ups != 1 || p.os != 1) return RYOLO_EINVAL;
+            RYOLO_CONV_DRY_RUN(lc, code);
+            return launch_kernel<conv_igemm_kernel<KS, BM, BN, WGM, WGN, NSTAGE, true, false, true>>(grid, block, smem, lc.stream, p, *lc.bnred);
         } else {
             return RYOLO_EINVAL;
         }
     }
-    RYOLO_CONV_DRY_RUN((RYOLO_CONV_KERNEL_IGEMM + igemm_tile_code<BM, BN, WGM, WGN, NSTAGE>()));
-    constexpr int STAGE = (BM + BN) * BK * 2;
-    constexpr size_t smem = NSTAGE * STAGE;
-    static bool attr_done = false;
-    auto kfn = conv_igemm_kernel<KS, BM, BN, WGM, WGN, NSTAGE, FAST, GEN>;
-    if (!attr_done) {
-        if (smem > 64 * 1024 &&
-            hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return RYOLO_ELAUNCH;
-        attr_done = true;
-    }
-    const int mt = (p.M + BM - 1) / BM;
-    p.nt = (p.Cout + BN - 1) / BN;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)(mt * p.nt)), dim3(WGM * WGN * 64), smem, stream, p, BnRed());
-    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
-}
-
-inline int cu_count() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-    }
-    return cus;
+    RYOLO_CONV_DRY_RUN(lc, code);
+    return launch_kernel<conv_igemm_kernel<KS, BM, BN, WGM, WGN, NSTAGE, FAST, GEN>>(grid, block, smem, lc.stream, p, BnRed());
 }
 
 inline unsigned magic_u32(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 
+// the persistent kernel's instantiations: plain for every tile; with statistics for the 4-wave tiles (1x1 layers, short-K 3x3 layers);
+// with the folded BatchNorm reduce (bnreduce_plan mode 2) for the 1x1 128 x 128 2x2 tile.  Anything else is EINVAL, dry run or not.
 template <int KS, int BM, int BN, int WGM, int WGN>
-int launch_persist(ConvParams &p, int grid, hipStream_t stream) {
+int launch_persist(ConvParams &p, int grid, const ConvLaunch &lc) {
     constexpr size_t smem = 2 * (BM + BN) * BK * 2;
-    if (g_conv_choice) {         // the instantiations below exist for these shapes only: report what would really be launched
-        const bool ok = g_bnred ? (g_bnred_mode == 2 && KS == 1 && BM == 128 && BN == 128 && WGM == 2 && WGN == 2 && !p.stat_part && p.ups == 1)
-                                : (!p.stat_part || WGM * WGN == 4);
-        if (!ok) return RYOLO_EINVAL;
-        RYOLO_CONV_DRY_RUN((RYOLO_CONV_KERNEL_IGEMM + igemm_tile_code<BM, BN, WGM, WGN, 2>()));
-    }
-    if (g_bnred) {
+    constexpr int code = RYOLO_CONV_KERNEL_IGEMM + igemm_tile_code<BM, BN, WGM, WGN, 2>();
+    const dim3 g((unsigned)grid), b(WGM * WGN * 64);
+    if (lc.bnred) {
         if constexpr (KS == 1 && BM == 128 && BN == 128 && WGM == 2 && WGN == 2) {
-            if (p.stat_part || p.ups != 1 || g_bnred_mode != 2) return RYOLO_EINVAL;
+            if (p.stat_part || p.ups != 1 || lc.bnred_mode != 2) return RYOLO_EINVAL;
+            RYOLO_CONV_DRY_RUN(lc, code);
             constexpr size_t smem_bn = smem + (size_t)WGM * WGN * (BN / 8) * 24 * 4;
-            static bool attr_bn = false;
-            if (!attr_bn) {
-                if (hipFuncSetAttribute((const void *)conv_igemm_persist_kernel<KS, BM, BN, WGM, WGN, false, true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_bn) != hipSuccess)
-                    return RYOLO_ELAUNCH;
-                attr_bn = true;
-            }
-            hipLaunchKernelGGL((conv_igemm_persist_kernel<KS, BM, BN, WGM, WGN, false, true>), dim3((unsigned)grid), dim3(WGM * WGN * 64),
-                               smem_bn, stream, p, *g_bnred);
-            return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+            return launch_kernel<conv_igemm_persist_kernel<KS, BM, BN, WGM, WGN, false, true>>(g, b, smem_bn, lc.stream, p, *lc.bnred);
         } else {
             return RYOLO_EINVAL;
         }
     }
-    if constexpr (WGM * WGN == 4) {     // the statistics instantiation exists for the 4-wave tiles (1x1 layers, short-K 3x3 layers)
+    if constexpr (WGM * WGN == 4) {
         if (p.stat_part) {
+            RYOLO_CONV_DRY_RUN(lc, code);
             constexpr size_t smem_st = smem + (size_t)WGM * 2 * BN * 4;
-            static bool attr_done = false;
-            if (!attr_done) {
-                if (hipFuncSetAttribute((const void *)conv_igemm_persist_kernel<KS, BM, BN, WGM, WGN, true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_st) != hipSuccess)
-                    return RYOLO_ELAUNCH;
-                attr_done = true;
-            }
-            hipLaunchKernelGGL((conv_igemm_persist_kernel<KS, BM, BN, WGM, WGN, true>), dim3((unsigned)grid), dim3(WGM * WGN * 64), smem_st, stream, p);
-            return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+            return launch_kernel<conv_igemm_persist_kernel<KS, BM, BN, WGM, WGN, true>>(g, b, smem_st, lc.stream, p, BnRed());
         }
     }
     if (p.stat_part) return RYOLO_EINVAL;
-    hipLaunchKernelGGL((conv_igemm_persist_kernel<KS, BM, BN, WGM, WGN, false>), dim3((unsigned)grid), dim3(WGM * WGN * 64), smem, stream, p);
-    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+    RYOLO_CONV_DRY_RUN(lc, code);
+    return launch_kernel<conv_igemm_persist_kernel<KS, BM, BN, WGM, WGN, false>>(g, b, smem, lc.stream, p, BnRed());
 }
 
 template <int KS, int BM, int BN, int WGM, int WGN, int NSTAGE = 2>
-int launch_variant(ConvParams &p, hipStream_t stream) {
+int launch_variant(ConvParams &p, const ConvLaunch &lc) {
     const bool gen = p.stat_part != nullptr || p.os != 1;
     {
         const long long dmax = p.Wo > p.Ho ? p.Wo : p.Ho, mpad = ((long long)p.M + BM - 1) / BM * BM;
@@ -1423,27 +1362,22 @@ int launch_variant(ConvParams &p, hipStream_t stream) {
     // (the training forward of a 1x1 layer takes it too: the 4-wave tiles have a statistics instantiation)
     const bool persist_ok = p.os == 1 && (!p.stat_part || (WGM * WGN == 4 && !p.res));
     if constexpr (NSTAGE == 2 && BM * BN * 2 <= (BM + BN) * BK * 2) if (p.fast && persist_ok && !p.no_persist && (KS == 1 || p.force_persist)) {
-        // persistent grid when there is more than one round of tiles and the multiply-high divisions are exact
-        const int mt = (p.M + BM - 1) / BM, nt = (p.Cout + BN - 1) / BN;
-        const long long T = (long long)mt * nt;
-        const int grid = (2 * cu_count()) & ~7;
-        const long long dmax = p.Wo > p.Ho ? p.Wo : p.Ho;
-        // ... and only when the tile list is at least 2.5 rounds deep (measured: 1444 tiles 0.030 -> 0.028 ms, 722 tiles
-        // 0.021 -> 0.022), with the 4-wave layout (the 8-wave persistent variant is slower: 0.031)
-        const bool deep = p.force_persist ? T > grid : 2 * T >= 5 * grid;
-        if (deep && grid >= 8 && ((long long)mt * BM) * dmax < 0x100000000ll && T * nt < 0x100000000ll) {
-            p.nt = nt;
-            p.ntiles = (int)T;
-            p.magic_wo = magic_u32(p.Wo); p.magic_ho = magic_u32(p.Ho); p.magic_nt = magic_u32(nt);
-            return launch_persist<KS, BM, BN, WGM, WGN>(p, grid, stream);
+        // ... when the tile list is deep enough and the multiply-high divisions are exact (persist_grid), with the 4-wave layout
+        // (the 8-wave persistent variant is slower: 0.031)
+        const PersistGrid pg = persist_grid(p.M, BM, p.Cout, BN, p.Ho, p.Wo, p.force_persist != 0);
+        if (pg.deep && pg.exact) {
+            p.nt = pg.nt;
+            p.ntiles = (int)pg.tiles;
+            p.magic_nt = magic_u32(pg.nt);
+            return launch_persist<KS, BM, BN, WGM, WGN>(p, pg.grid, lc);
         }
     }
     if (p.fast) {
-        if (gen) return launch_variant_impl<KS, BM, BN, WGM, WGN, NSTAGE, true, true>(p, stream);
-        return launch_variant_impl<KS, BM, BN, WGM, WGN, NSTAGE, true, false>(p, stream);
+        if (gen) return launch_variant_impl<KS, BM, BN, WGM, WGN, NSTAGE, true, true>(p, lc);
+        return launch_variant_impl<KS, BM, BN, WGM, WGN, NSTAGE, true, false>(p, lc);
     }
-    if (gen) return launch_variant_impl<KS, BM, BN, WGM, WGN, NSTAGE, false, true>(p, stream);
-    return launch_variant_impl<KS, BM, BN, WGM, WGN, NSTAGE, false, false>(p, stream);
+    if (gen) return launch_variant_impl<KS, BM, BN, WGM, WGN, NSTAGE, false, true>(p, lc);
+    return launch_variant_impl<KS, BM, BN, WGM, WGN, NSTAGE, false, false>(p, lc);
 }
 
 }  // namespace
@@ -1521,11 +1455,11 @@ int ryolo_nhwc_bf16_to_nchw_f32(const void *x, int N, int C, int H, int W, int c
     return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
 }
 
-static int pick_tile(const ryolo_conv_desc *d, int cout) {
-    (void)cout;
+}  // extern "C"
+
+static int pick_tile(const ryolo_conv_desc *d) {
     return d->tile & 0xff;   // 0 = auto (dispatch decides); bit 8 (0x100) forces the general (slow-address) path, for tests
 }
-
 
 // Which 256-channel tile a 3x3 layer takes: conv_mp.hip (one 8-wave workgroup per CU, 256 or 192 pixel rows) or conv_mq.hip (two
 // 4-wave workgroups per CU, 128 rows).  Estimated launch time = (tiles of the busiest CU) x (time per tile), time per tile
@@ -1561,7 +1495,7 @@ static int pick_wide_tile(const ConvParams &p) {
 
 static long long g_nt_out_min = NT_OUT_MIN_BYTES;      // (settable in ablation builds: ryolo_debug_conv_nt_min)
 // (measurement build: RYOLO_NT_OUT_MIN_MB overrides the threshold (MiB) per call -- the in-chain sweep of tools/step_ab.py, profiles/r05_ab_log.txt)
-static inline long long nt_out_min_bytes() {
+long long ryolo_detail::nt_out_min_bytes() {
     const char *e = abl_env("RYOLO_NT_OUT_MIN_MB");
     return e ? (long long)atoll(e) << 20 : g_nt_out_min;
 }
@@ -1572,12 +1506,10 @@ extern "C" void ryolo_debug_conv_nt_min(long long bytes) { g_nt_out_min = bytes;
 #endif
 
 // RYOLO_CONV1X1 = igemm keeps the 1x1 layers on the 128 x 128 tiles (A/B timing; ryolo_set_tuning)
-static bool conv_pw_disabled() {
+bool ryolo_detail::conv_pw_disabled() {
     const char *e = tune(TUNE_CONV1X1);
     return e && !strcmp(e, "igemm");
 }
-
-
 
 // conv_mq.hip's 128-channel tiles (round 5).  RYOLO_MQ128 = 0 (default): off -- the 128 x 128 / 256 x 64 tiles of this file as in round 4;
 // 1: the 3x3 layers and data gradients with C_out % 256 != 0; 2: also the 1x1 layers whose 128-pixel tile list is short (38^2 / 19^2).
@@ -1585,14 +1517,13 @@ static bool conv_pw_disabled() {
 // off / 49.59 on / 49.85 with the 1x1 layers; bs-32 forward 6.08 / 6.07 / 6.30 ms): with 32 channels per wave a K tile moves 0.625 KiB of
 // LDS fragments per MFMA against 0.375 for the 256-channel tile -- the LDS pipe, not the schedule, bounds these layers.
 // MEASUREMENT BUILD ONLY (round 6): the shipped library has neither the switch nor the instantiations (launch_conv_mq128 returns EINVAL).
-static int mq128_knob() {
+int ryolo_detail::mq128_knob() {
     const char *e = abl_env("RYOLO_MQ128");
     return e ? atoi(e) : 0;
 }
 // pixels per tile: 64 when the list of 128-pixel tiles is less than 2.5 rounds of the two-workgroups-per-CU grid deep
 static int mq128_pick_bm(const ConvParams &p) {
-    const long long t128 = (((long long)p.M + 127) / 128) * (p.Cout / 128), grid = (2 * cu_count()) & ~7;
-    return 2 * t128 >= 5 * grid ? 128 : 64;
+    return persist_grid(p.M, 128, p.Cout, 128, p.Ho, p.Wo).deep ? 128 : 64;
 }
 // does the auto dispatch send this launch to the 128-channel family?  (3x3: every eligible shape the 256-channel tiles do not serve;
 // 1x1 (knob 2): K >= 256 and a short tile list -- the 76^2 layers stay on conv_pw.hip, HBM-bound and at their floor there)
@@ -1601,8 +1532,7 @@ static bool mq128_auto(const ConvParams &p, int ksize) {
     if (knob <= 0 || !conv_mq128_eligible(p)) return false;
     if (ksize == 3) return !conv_mp_eligible(p);
     if (knob < 2 || p.Kpad < 4 * BK) return false;
-    const long long t128 = (((long long)p.M + 127) / 128) * (p.Cout / 128), grid = (2 * cu_count()) & ~7;
-    return t128 < 4 * grid;
+    return !persist_grid(p.M, 128, p.Cout, 128, p.Ho, p.Wo, false, 8).deep;      // fewer than FOUR rounds of 128-pixel tiles
 }
 
 // RYOLO_CONV0=direct keeps layer 0 on conv3x3_c8_direct_kernel (fragments from global memory); default: the LDS-staged kernel of
@@ -1612,40 +1542,45 @@ static bool conv0_halo_on() {
     return !(e && !strcmp(e, "direct"));
 }
 
-static int dispatch(ConvParams &p, int ksize, int pick, hipStream_t stream) {
+int ryolo_detail::dispatch(ConvParams &p, int ksize, int pick, const ConvLaunch &lc) {
+    const BnRed *const bnred = lc.bnred;
     // the stem kernel (conv_stem.hip: 3x3, 32 -> 64 channels, input patch staged once): auto and pick 12
-    const bool stem = (pick == 0 || pick == 12) && conv_stem_eligible(p, ksize) && !g_bnred;
+    const bool stem = (pick == 0 || pick == 12) && conv_stem_eligible(p, ksize) && !bnred;
     if (pick == 12 && !stem) return RYOLO_EINVAL;
-    if (g_bnred && g_bnred_mode == 3) p.no_persist = 1;          // the reduce rides in the one-tile-per-workgroup kernel
+    if (bnred && lc.bnred_mode == 3) p.no_persist = 1;          // the reduce rides in the one-tile-per-workgroup kernel
     // the weight-stationary 1x1 kernel (conv_pw.hip): auto and pick 13; RYOLO_CONV1X1 = igemm keeps the 128x128 tiles (A/B timing, tests)
-    const bool pw = ((pick == 0 && !conv_pw_disabled()) || pick == 13) && conv_pw_eligible(p, ksize) && (pick == 13 || (g_bnred ? g_bnred_mode == 1 : conv_pw_preferred(p)));
+    const bool pw = ((pick == 0 && !conv_pw_disabled()) || pick == 13) && conv_pw_eligible(p, ksize) && (pick == 13 || (bnred ? lc.bnred_mode == 1 : conv_pw_preferred(p)));
     if (pick == 13 && !pw) return RYOLO_EINVAL;
-    if (stem) return launch_conv_stem(p, cu_count(), stream);
+    if (stem) return launch_conv_stem(p, lc);
     // conv_stem.hip's 3x3 / 1 64 -> 128 kernel (round 6): auto and pick 17 (measurement build: RYOLO_STEM64=0 keeps the 128 x 128 tiles, A/B timing)
     {
         const char *e64 = abl_env("RYOLO_STEM64");
-        const bool stem64 = ((pick == 0 && !(e64 && !strcmp(e64, "0"))) || pick == 17) && conv_stem64_eligible(p, ksize) && !g_bnred;
+        const bool stem64 = ((pick == 0 && !(e64 && !strcmp(e64, "0"))) || pick == 17) && conv_stem64_eligible(p, ksize) && !bnred;
         if (pick == 17 && !stem64) return RYOLO_EINVAL;
-        if (stem64) return launch_conv_stem64(p, cu_count(), stream);
+        if (stem64) return launch_conv_stem64(p, lc);
     }
     // conv_mq.hip's 128-channel tiles: picks 15 (128 pixels) / 16 (64 pixels); auto per mq128_auto(); with the folded reduce only as
     // bnreduce_plan's mode 4 (its caller sized the partial rows for that grid)
-    if (pick == 15 || pick == 16) return launch_conv_mq128(p, pick == 15 ? 128 : 64, g_bnred_mode == 4 ? g_bnred : nullptr, stream);
-    if (pick == 0 && (g_bnred ? g_bnred_mode == 4 : mq128_auto(p, ksize))) {
-        const int r = launch_conv_mq128(p, mq128_pick_bm(p), g_bnred, stream);
-        if (r != RYOLO_EINVAL || g_bnred) return r;              // EINVAL: a size guard -- the tiles below take those
+    if (pick == 15 || pick == 16) {
+        ConvLaunch l = lc;
+        if (lc.bnred_mode != 4) l.bnred = nullptr;
+        return launch_conv_mq128(p, pick == 15 ? 128 : 64, l);
+    }
+    if (pick == 0 && (bnred ? lc.bnred_mode == 4 : mq128_auto(p, ksize))) {
+        const int r = launch_conv_mq128(p, mq128_pick_bm(p), lc);
+        if (r != RYOLO_EINVAL || bnred) return r;              // EINVAL: a size guard -- the tiles below take those
     }
     if (pw) {
-        const int r = launch_conv_pw(p, g_bnred, stream);
-        if (r != RYOLO_EINVAL || pick == 13 || g_bnred) return r;      // EINVAL: a size guard (2 GiB slices) -- the 128x128 tiles take those
+        const int r = launch_conv_pw(p, lc);
+        if (r != RYOLO_EINVAL || pick == 13 || bnred) return r;      // EINVAL: a size guard (2 GiB slices) -- the 128x128 tiles take those
                                                                         // (not with the folded reduce: its caller sized the partial rows for THIS grid)
     }
     if (pick == 0) {
         // auto: 3x3 layers with 256-multiple output channels take one of the persistent multi-phase tiles (the 1x1 layers are
         // faster on the 128x128 tiles, tools/mp_tune.py)
-        if (ksize == 3 && conv_mp_eligible(p) && !g_bnred) {
+        if (ksize == 3 && conv_mp_eligible(p) && !bnred) {
             const int bm = pick_wide_tile(p);
-            const int r = bm == 0 ? launch_conv_mq(p, 0, stream) : launch_conv_mp(p, bm, 0, stream);
+            const int r = bm == 0 ? launch_conv_mq(p, 0, lc) : launch_conv_mp(p, bm, 0, lc);
             if (r != RYOLO_EINVAL) return r;      // EINVAL: a size guard of the persistent tiles (2 GiB output slices, 2^32 pixel*extent) -- the 128x128 tiles take those
         }
         pick = p.Cout <= 32 ? 3 : (p.Cout <= 64 ? 2 : 1);
@@ -1660,39 +1595,38 @@ static int dispatch(ConvParams &p, int ksize, int pick, hipStream_t stream) {
         }
     }
     // picks 8 / 11 / 14: the 256-channel multi-phase tile of conv_mp.hip with BM 256 / BM 192 / BM picked per shape (tests, A/B timing)
-    if (pick == 8) return launch_conv_mp(p, 256, 0, stream);
-    if (pick == 11) return launch_conv_mp(p, 192, 0, stream);
-    if (pick == 14) return launch_conv_mp(p, 0, 0, stream);
-    if (pick == 9) return launch_conv_mq(p, 0, stream);      // the two-workgroups-per-CU tile of conv_mq.hip
+    if (pick == 8) return launch_conv_mp(p, 256, 0, lc);
+    if (pick == 11) return launch_conv_mp(p, 192, 0, lc);
+    if (pick == 14) return launch_conv_mp(p, 0, 0, lc);
+    if (pick == 9) return launch_conv_mq(p, 0, lc);      // the two-workgroups-per-CU tile of conv_mq.hip
 #ifdef RYOLO_MP_ABLATION
-    if (pick >= 32 && pick < 64) return launch_conv_mp(p, (pick & 16) ? 192 : 256, ryolo_mp_ablation_variant(pick & 15), stream);
-    if (pick >= 64 && pick < 80) return launch_conv_mq(p, ryolo_mp_ablation_variant(pick & 15), stream);
+    if (pick >= 32 && pick < 64) return launch_conv_mp(p, (pick & 16) ? 192 : 256, ryolo_mp_ablation_variant(pick & 15), lc);
+    if (pick >= 64 && pick < 80) return launch_conv_mq(p, ryolo_mp_ablation_variant(pick & 15), lc);
 #endif
     if (ksize == 1) {
         if (pick == 1) {   // 8 waves of 64 pixels x 32 channels, except where the (4-wave) persistent grid wins
-            const long long T = (((long long)p.M + 127) / 128) * ((p.Cout + 127) / 128);
-            if (p.fast && p.os == 1 && !(p.stat_part && p.res) && !p.no_persist && (p.force_persist || 2 * T >= 5 * (long long)((2 * cu_count()) & ~7)))
-                return launch_variant<1, 128, 128, 2, 2>(p, stream);
+            if (p.fast && p.os == 1 && !(p.stat_part && p.res) && !p.no_persist && (p.force_persist || persist_grid(p.M, 128, p.Cout, 128, p.Ho, p.Wo).deep))
+                return launch_variant<1, 128, 128, 2, 2>(p, lc);
             p.no_persist = 1;
-            return launch_variant<1, 128, 128, 2, 4>(p, stream);
+            return launch_variant<1, 128, 128, 2, 4>(p, lc);
         }
-        if (pick == 7) return launch_variant<1, 128, 128, 2, 2>(p, stream);
-        if (pick == 2) return launch_variant<1, 256, 64, 4, 1>(p, stream);
-        if (pick == 3) return launch_variant<1, 256, 32, 4, 1>(p, stream);
-        if (pick == 4) return launch_variant<1, 256, 128, 4, 2, 3>(p, stream);
-        if (pick == 6) return launch_variant<1, 128, 128, 4, 2>(p, stream);
+        if (pick == 7) return launch_variant<1, 128, 128, 2, 2>(p, lc);
+        if (pick == 2) return launch_variant<1, 256, 64, 4, 1>(p, lc);
+        if (pick == 3) return launch_variant<1, 256, 32, 4, 1>(p, lc);
+        if (pick == 4) return launch_variant<1, 256, 128, 4, 2, 3>(p, lc);
+        if (pick == 6) return launch_variant<1, 128, 128, 4, 2>(p, lc);
     } else {
-        if (pick == 1) return launch_variant<3, 128, 128, 2, 4>(p, stream);
-        if (pick == 7) return launch_variant<3, 128, 128, 2, 2>(p, stream);
-        if (pick == 2) return launch_variant<3, 256, 64, 4, 1>(p, stream);
-        if (pick == 3) return launch_variant<3, 256, 32, 4, 1>(p, stream);
-        if (pick == 4) return launch_variant<3, 256, 128, 4, 2, 3>(p, stream);
-        if (pick == 6) return launch_variant<3, 128, 128, 4, 2>(p, stream);
+        if (pick == 1) return launch_variant<3, 128, 128, 2, 4>(p, lc);
+        if (pick == 7) return launch_variant<3, 128, 128, 2, 2>(p, lc);
+        if (pick == 2) return launch_variant<3, 256, 64, 4, 1>(p, lc);
+        if (pick == 3) return launch_variant<3, 256, 32, 4, 1>(p, lc);
+        if (pick == 4) return launch_variant<3, 256, 128, 4, 2, 3>(p, lc);
+        if (pick == 6) return launch_variant<3, 128, 128, 4, 2>(p, lc);
     }
     return RYOLO_EINVAL;
 }
 
-static int validate(const ryolo_conv_desc *d) {
+int ryolo_detail::conv_validate(const ryolo_conv_desc *d) {
     if (!d) return RYOLO_EINVAL;
     if (d->ksize != 1 && d->ksize != 3) return RYOLO_EINVAL;
     if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->stride <= 0) return RYOLO_EINVAL;
@@ -1703,109 +1637,144 @@ static int validate(const ryolo_conv_desc *d) {
     return RYOLO_OK;
 }
 
-int ryolo_conv_stat_rows(const ryolo_conv_desc *d) {
-    if (validate(d) != RYOLO_OK) return 0;
-    return STAT_ROWS;
+// The shape part of a launch from its descriptor: tensor geometry, the GEMM sizes, the regular tap window, dense output placement, the
+// epilogue.  Everything else of `p` is the caller's (value-initialised: what a path does not set is zero).  False: no output pixels, or
+// more than the 31-bit pixel index holds.
+static bool conv_shape(const ryolo_conv_desc *d, ConvParams &p) {
+    p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.in_cs = d->in_cstride;
+    p.stride = d->stride; p.pad = d->pad;
+    p.Ho = (d->H + 2 * d->pad - d->ksize) / d->stride + 1;
+    p.Wo = (d->W + 2 * d->pad - d->ksize) / d->stride + 1;
+    if (p.Ho <= 0 || p.Wo <= 0) return false;
+    p.Cout = d->Cout; p.out_cs = d->out_cstride; p.res_cs = d->res_cstride;
+    p.K = d->ksize * d->ksize * d->Cin;
+    p.Kpad = (p.K + BK - 1) / BK * BK;
+    const long long M = (long long)d->N * p.Ho * p.Wo;
+    if (M > 0x7fffffffLL - 512) return false;
+    p.M = (int)M;
+    p.ntaps = d->ksize * d->ksize;
+    for (int t = 0; t < 9; t++) { p.tap_dy[t] = t / d->ksize; p.tap_dx[t] = t % d->ksize; }
+    p.os = 1; p.osx = 1; p.ooy = 0; p.oox = 0; p.OH = p.Ho; p.OW = p.Wo;
+    p.act = d->act; p.slope = d->slope; p.ups = d->upsample;
+    return true;
 }
 
-int ryolo_conv2d_bn_act_stats(const ryolo_conv_desc *d, const void *x, const void *w_packed, const float *scale,
-                              const float *shift, const void *residual, void *y, double *stat_part, void *stream_) {
-    if (validate(d) != RYOLO_OK || !x || !w_packed || !scale || !shift) return RYOLO_EINVAL;
-    if (!y && !(stat_part && ryolo_conv0_recompute_supported(d))) return RYOLO_EINVAL;     // y == NULL: statistics only, layer-0 kernel only
+// Darknet-53 layer 0 as conv3x3_c8_direct_kernel / conv0_halo_kernel serve it: 3x3 / 1 pad 1, 8 (padded) -> 32 channels, rows of at
+// least 16 pixels, 32-bit buffer offsets over x and y (out_cs: the pixel stride of what the launch writes)
+static bool conv0_shape(const ryolo_conv_desc *d, int out_cs) {
+    const unsigned long long M = (unsigned long long)d->N * d->H * d->W;
+    return d->ksize == 3 && d->stride == 1 && d->pad == 1 && d->Cin == 8 && d->in_cstride == 8 && d->Cout == 32 && d->upsample == 1 &&
+           !(d->tile & 0x1ff) && d->W >= 16 && buffer_extent(M, 8, 8) && buffer_extent(M, out_cs, 32);
+}
+// ... and its launch: the two descriptors (the second one covers y), 16-pixel groups, gpw of them per wave, 4 waves per block
+static bool conv0_params(const ryolo_conv_desc *d, int out_cs, ConvParams &p, int gpw, unsigned *nblk) {
+    if (!conv_shape(d, p) || !buffer_extent(p.M, 8, 8, &p.x_bytes) || !buffer_extent(p.M, out_cs, 32, &p.w_bytes)) return false;
+    p.out_cs = out_cs; p.res_cs = 0;
+    p.nt_out = (long long)p.M * 64 >= nt_out_min_bytes() ? 1 : 0;
+    const long long groups = ((long long)p.M + 15) / 16, waves = (groups + gpw - 1) / gpw;
+    *nblk = (unsigned)((waves + 3) / 4);
+    return true;
+}
+
+// the forward launch behind ryolo_conv2d_bn_act_stats and ryolo_conv_kernel_choice (lc.choice: only whether residual / stat_part are
+// null matters then -- nothing is dereferenced before the launch site)
+static int conv_forward(const ryolo_conv_desc *d, const void *x, const void *w_packed, const float *scale, const float *shift,
+                        const void *residual, void *y, double *stat_part, const ConvLaunch &lc) {
+    if (conv_validate(d) != RYOLO_OK) return RYOLO_EINVAL;
     if (residual && ((d->res_cstride & 7) || d->res_cstride < d->Cout)) return RYOLO_EINVAL;
-    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w_packed | (uintptr_t)residual | (uintptr_t)scale | (uintptr_t)shift) & 15)
-        return RYOLO_EINVAL;
-    ConvParams p;
+    ConvParams p{};
     p.x = (const __bf16 *)x;
     p.w = (const __bf16 *)w_packed;
     p.scale = scale;
     p.shift = shift;
     p.res = (const __bf16 *)residual;
     p.y = (__bf16 *)y;
-    p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.in_cs = d->in_cstride;
-    p.stride = d->stride;
-    p.pad = d->pad;
-    p.Ho = (d->H + 2 * d->pad - d->ksize) / d->stride + 1;
-    p.Wo = (d->W + 2 * d->pad - d->ksize) / d->stride + 1;
-    if (p.Ho <= 0 || p.Wo <= 0) return RYOLO_EINVAL;
-    p.Cout = d->Cout; p.out_cs = d->out_cstride; p.res_cs = d->res_cstride;
-    p.K = d->ksize * d->ksize * d->Cin;
-    p.Kpad = (p.K + BK - 1) / BK * BK;
-    const long long M = (long long)d->N * p.Ho * p.Wo;
-    if (M > 0x7fffffffLL - 512) return RYOLO_EINVAL;
-    p.M = (int)M;
+    p.stat_part = stat_part;
+    if (!residual && conv0_shape(d, d->out_cstride)) {
+        // Darknet-53 layer 0: fragments straight from global memory (conv3x3_c8_direct_kernel); 32-bit buffer offsets
+        const int gpw = (d->tile >> 16) ? (d->tile >> 16) : 32;   // groups of 16 pixels per wave (upper tile bits: tuning)
+        unsigned nblk;
+        if (!conv0_params(d, d->out_cstride, p, gpw, &nblk)) return RYOLO_EINVAL;
+        p.cin_log2 = 3;
+        p.stat_cpad = 128;
+        const bool staged = conv0_halo_on() && !(d->tile >> 16) && y && !stat_part;
+        RYOLO_CONV_DRY_RUN(lc, (staged ? RYOLO_CONV_KERNEL_STEM0 : RYOLO_CONV_KERNEL_DIRECT8));
+        // (the statistics-only pass stays on the direct kernel: 284 us against 320 for the staged one -- that pass is bound by its per-element
+        // arithmetic, not by the fragment path)
+        // (... and so do the statistics of the stored-z form: the two statistics passes must add the same values in the same order)
+        if (staged) return launch_conv0_halo(p, nullptr, 0, lc);
+        return stat_part ? launch_c8_direct<true>(p, gpw, nblk, lc.stream) : launch_c8_direct<false>(p, gpw, nblk, lc.stream);
+    }
+    if (!conv_shape(d, p)) return RYOLO_EINVAL;
     p.cin_log2 = ilog2_exact(d->Cin);
     if (d->ksize == 3 && p.cin_log2 < 0 && (d->Cin % BK)) return RYOLO_EINVAL;
-    p.act = d->act; p.slope = d->slope; p.ups = d->upsample; p.nt = 0;
-    {
-        const unsigned long long xb = (((unsigned long long)d->N * d->H * d->W - 1) * d->in_cstride + d->Cin) * 2ull;
-        const unsigned long long wb = ((unsigned long long)((d->Cout + 127) / 128 * 128) * p.Kpad + 128) * 2ull;
-        p.taps2 = (d->Cin == 32 && d->ksize == 3) ? 1 : 0;
-        p.fast = (d->Cin % BK == 0 || p.taps2) && xb < 0x7fffff00ull && wb < 0x7fffff00ull && !(d->tile & 0x100);
-        if (!p.fast) p.taps2 = 0;
-        p.x_bytes = (unsigned)(p.fast ? xb : 0);
-        p.w_bytes = (unsigned)(p.fast ? wb : 0);
-    }
-    p.ntaps = d->ksize * d->ksize;
-    for (int t = 0; t < 9; t++) { p.tap_dy[t] = t / d->ksize; p.tap_dx[t] = t % d->ksize; }
-    p.os = 1; p.osx = 1; p.ooy = 0; p.oox = 0; p.OH = p.Ho; p.OW = p.Wo;
+    p.taps2 = (d->Cin == 32 && d->ksize == 3) ? 1 : 0;
+    p.fast = (d->Cin % BK == 0 || p.taps2) && !(d->tile & 0x100) && buffer_extent((unsigned long long)d->N * d->H * d->W, d->in_cstride, d->Cin, &p.x_bytes) &&
+             buffer_extent((d->Cout + 127) / 128 * 128, p.Kpad, p.Kpad + 128, &p.w_bytes);
+    if (!p.fast) p.taps2 = p.x_bytes = p.w_bytes = 0;
     p.no_persist = (d->tile & 0x200) ? 1 : 0;
     p.force_persist = (d->tile & 0x800) ? 1 : 0;
     p.pw_grid_cap = (d->tile & 0xff) == 13 ? (d->tile >> 16) & 0xff : 0;
 #ifdef RYOLO_MP_ABLATION
     if ((d->tile & 0x400) && p.fast) p.x_bytes = p.w_bytes = 0;   // timing experiment: every load out of range (zeros, no traffic)
 #endif
-    p.ntiles = 0; p.magic_wo = p.magic_ho = p.magic_nt = 0;
     p.nt_out = (long long)p.M * d->upsample * d->upsample * d->Cout * 2 >= nt_out_min_bytes() ? 1 : 0;
-    p.stat_part = stat_part;
     p.stat_cpad = (d->Cout + 127) / 128 * 128;
-    const unsigned long long c8_xb = (unsigned long long)d->N * d->H * d->W * 16ull, c8_yb = ((unsigned long long)(p.M - 1) * d->out_cstride + 32) * 2ull;
-    if (d->ksize == 3 && d->stride == 1 && d->pad == 1 && d->Cin == 8 && d->in_cstride == 8 && d->Cout == 32 &&
-        !residual && d->upsample == 1 && !(d->tile & 0x1ff) && p.Wo >= 16 && c8_xb < 0x7fffff00ull && c8_yb < 0x7fffff00ull) {
-        // Darknet-53 layer 0: fragments straight from global memory (conv3x3_c8_direct_kernel); 32-bit buffer offsets
-        p.x_bytes = (unsigned)c8_xb;
-        p.w_bytes = (unsigned)c8_yb;                          // this kernel's second descriptor covers y
-        const long long groups = ((long long)p.M + 15) / 16;
-        const int gpw = (d->tile >> 16) ? (d->tile >> 16) : 32;   // groups of 16 pixels per wave (upper tile bits: tuning)
-        const long long waves = (groups + gpw - 1) / gpw;
-        const unsigned nblk = (unsigned)((waves + 3) / 4);
-        const bool staged = conv0_halo_on() && !(d->tile >> 16) && y && !stat_part;
-        RYOLO_CONV_DRY_RUN((staged ? RYOLO_CONV_KERNEL_STEM0 : RYOLO_CONV_KERNEL_DIRECT8));
-        // (the statistics-only pass stays on the direct kernel: 284 us against 320 for the staged one -- that pass is bound by its per-element
-        // arithmetic, not by the fragment path)
-        // (... and so do the statistics of the stored-z form: the two statistics passes must add the same values in the same order)
-        if (staged) return launch_conv0_halo(p, nullptr, 0, cu_count(), (hipStream_t)stream_);
-        return stat_part ? launch_c8_direct<true>(p, gpw, nblk, (hipStream_t)stream_) : launch_c8_direct<false>(p, gpw, nblk, (hipStream_t)stream_);
-    }
-    return dispatch(p, d->ksize, pick_tile(d, d->Cout), (hipStream_t)stream_);
+    return dispatch(p, d->ksize, pick_tile(d), lc);
 }
 
+// a YOLO head as conv_pw.hip's decode launch sees it: 1x1 / 1, K = C_in a multiple of 64, dense output rows
 static bool head_params(const ryolo_conv_desc *d, ConvParams &p) {
-    if (validate(d) != RYOLO_OK || d->ksize != 1 || d->stride != 1 || d->pad != 0 || d->upsample != 1 || (d->Cin % BK)) return false;
-    p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.in_cs = d->in_cstride; p.stride = 1; p.pad = 0; p.Ho = d->H; p.Wo = d->W;
-    p.Cout = d->Cout; p.out_cs = d->Cout; p.res_cs = 0; p.K = d->Cin; p.Kpad = d->Cin;
-    const long long M = (long long)d->N * d->H * d->W;
-    if (M > 0x7fffffffLL - 512) return false;
-    p.M = (int)M;
-    p.act = d->act; p.slope = d->slope; p.ups = 1; p.nt = 0; p.taps2 = 0; p.os = 1; p.osx = 1; p.ooy = 0; p.oox = 0; p.OH = p.Ho; p.OW = p.Wo;
-    const unsigned long long xb = (((unsigned long long)M - 1) * d->in_cstride + d->Cin) * 2ull;
-    const unsigned long long wb = ((unsigned long long)((d->Cout + 127) / 128 * 128) * p.Kpad + 128) * 2ull;
-    if (xb >= 0x7fffff00ull || wb >= 0x7fffff00ull) return false;
-    p.fast = 1; p.x_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb;
-    p.res = nullptr; p.y = nullptr; p.stat_part = nullptr; p.stat_cpad = 0; p.nt_out = 0; p.pw_grid_cap = 0;
-    p.no_persist = 0; p.force_persist = 0; p.ntaps = 1; p.ntiles = 0; p.magic_wo = p.magic_ho = p.magic_nt = 0; p.use_magic = 1;
+    if (conv_validate(d) != RYOLO_OK || d->ksize != 1 || d->stride != 1 || d->pad != 0 || d->upsample != 1 || (d->Cin % BK)) return false;
+    if (!conv_shape(d, p)) return false;
+    p.out_cs = d->Cout; p.res_cs = 0; p.Kpad = d->Cin;
+    if (!buffer_extent(p.M, d->in_cstride, d->Cin, &p.x_bytes) || !buffer_extent((d->Cout + 127) / 128 * 128, p.Kpad, p.Kpad + 128, &p.w_bytes)) return false;
+    p.fast = 1; p.use_magic = 1;
     return true;
 }
 
+extern "C" {
+
+int ryolo_conv_stat_rows(const ryolo_conv_desc *d) {
+    if (conv_validate(d) != RYOLO_OK) return 0;
+    return STAT_ROWS;
+}
+
+int ryolo_conv2d_bn_act_stats(const ryolo_conv_desc *d, const void *x, const void *w_packed, const float *scale,
+                              const float *shift, const void *residual, void *y, double *stat_part, void *stream_) {
+    if (!x || !w_packed || !scale || !shift) return RYOLO_EINVAL;
+    if (!y && !(stat_part && ryolo_conv0_recompute_supported(d))) return RYOLO_EINVAL;     // y == NULL: statistics only, layer-0 kernel only
+    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w_packed | (uintptr_t)residual | (uintptr_t)scale | (uintptr_t)shift) & 15)
+        return RYOLO_EINVAL;
+    ConvLaunch lc;
+    lc.stream = (hipStream_t)stream_;
+    return conv_forward(d, x, w_packed, scale, shift, residual, y, stat_part, lc);
+}
+
+int ryolo_conv2d_bn_act(const ryolo_conv_desc *d, const void *x, const void *w_packed, const float *scale,
+                        const float *shift, const void *residual, void *y, void *stream_) {
+    return ryolo_conv2d_bn_act_stats(d, x, w_packed, scale, shift, residual, y, nullptr, stream_);
+}
+
+int ryolo_conv_kernel_choice(const ryolo_conv_desc *d, int with_residual, int with_statistics) {
+    int choice = -1;
+    ConvLaunch lc;
+    lc.choice = &choice;
+    void *fake = (void *)(uintptr_t)4096;      // never dereferenced: the dispatch returns before any launch
+    const int rc = conv_forward(d, fake, fake, (const float *)fake, (const float *)fake, with_residual ? fake : nullptr, fake,
+                                with_statistics ? (double *)fake : nullptr, lc);
+    return rc == RYOLO_OK ? choice : -1;
+}
+
 int ryolo_conv_head_decode_supported(const ryolo_conv_desc *d, int na, int no) {
-    ConvParams p;
+    ConvParams p{};
     return head_params(d, p) && conv_pw_decode_supported(p, na, no) ? 1 : 0;
 }
 
 int ryolo_conv_head_decode(const ryolo_conv_desc *d, const void *x, const void *w_packed, const float *scale, const float *shift,
                            const float *anchors, int na, int no, float stride, float context_factor, int arc, float *io,
                            long long io_rows_per_image, long long io_row_offset, float *pout, void *stream_) {
-    ConvParams p;
+    ConvParams p{};
     if (!x || !w_packed || !scale || !shift || !anchors || !io || !head_params(d, p) || !conv_pw_decode_supported(p, na, no)) return RYOLO_EINVAL;
     if (arc < 0 || arc > 2 || !(stride > 0.f) || !(context_factor > 0.f)) return RYOLO_EINVAL;
     if (((uintptr_t)x | (uintptr_t)w_packed) & 15) return RYOLO_EINVAL;
@@ -1814,46 +1783,32 @@ int ryolo_conv_head_decode(const ryolo_conv_desc *d, const void *x, const void *
 }
 
 int ryolo_conv_pair_supported(const ryolo_conv_desc *first, const ryolo_conv_desc *second, int shortcut_from_input) {
-    if (validate(first) != RYOLO_OK || validate(second) != RYOLO_OK) return 0;
+    if (conv_validate(first) != RYOLO_OK || conv_validate(second) != RYOLO_OK) return 0;
     return conv_stem_pair_kind(first, second, shortcut_from_input) != 0 ? 1 : 0;
 }
 
 int ryolo_conv2d_bn_act_pair(const ryolo_conv_desc *a, const ryolo_conv_desc *b, const void *x, const void *w_first, const float *scale_first,
                              const float *shift_first, const void *w_second, const float *scale_second, const float *shift_second,
                              int shortcut_from_input, void *y, void *stream_) {
-    if (validate(a) != RYOLO_OK || validate(b) != RYOLO_OK || !x || !w_first || !scale_first || !shift_first || !w_second || !scale_second ||
+    if (conv_validate(a) != RYOLO_OK || conv_validate(b) != RYOLO_OK || !x || !w_first || !scale_first || !shift_first || !w_second || !scale_second ||
         !shift_second || !y)
         return RYOLO_EINVAL;
     const int kind = conv_stem_pair_kind(a, b, shortcut_from_input);
     if (!kind) return RYOLO_EINVAL;
     if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w_first | (uintptr_t)w_second) & 15) return RYOLO_EINVAL;
-    ConvParams p;
-    p.x = nullptr; p.w = (const __bf16 *)w_second; p.scale = scale_second; p.shift = shift_second; p.res = nullptr; p.y = (__bf16 *)y;
-    p.N = b->N; p.H = b->H; p.W = b->W; p.Cin = b->Cin; p.in_cs = b->Cin; p.stride = b->stride; p.pad = b->pad;
-    p.Ho = (b->H + 2 * b->pad - 3) / b->stride + 1;
-    p.Wo = (b->W + 2 * b->pad - 3) / b->stride + 1;
-    p.Cout = b->Cout; p.out_cs = b->out_cstride; p.res_cs = 0;
-    p.K = 9 * b->Cin; p.Kpad = (p.K + BK - 1) / BK * BK;
-    p.M = (int)((long long)b->N * p.Ho * p.Wo);
-    p.act = b->act; p.slope = b->slope; p.ups = 1;
+    ConvParams p{};           // the second layer; its input is the first layer's output in LDS: dense, never in memory
+    if (!conv_shape(b, p)) return RYOLO_EINVAL;
+    p.w = (const __bf16 *)w_second; p.scale = scale_second; p.shift = shift_second; p.y = (__bf16 *)y;
+    p.in_cs = b->Cin; p.res_cs = 0;
     p.nt_out = (long long)p.M * b->Cout * 2 >= nt_out_min_bytes() ? 1 : 0;
-    p.stat_part = nullptr; p.stat_cpad = 0;
-    const unsigned long long xb = (((unsigned long long)a->N * a->H * a->W - 1) * a->in_cstride + a->Cin) * 2ull;
+    const unsigned long long xb = (((unsigned long long)a->N * a->H * a->W - 1) * a->in_cstride + a->Cin) * 2ull;   // (< 2^31: conv_stem_pair_kind)
     const int kpad_first = (a->ksize * a->ksize * a->Cin + BK - 1) / BK * BK;
     return launch_conv_stem_pair(kind, p, x, (unsigned)xb, a->in_cstride, a->H, a->W, w_first, kpad_first, scale_first, shift_first, a->act,
-                                 a->slope, cu_count(), (hipStream_t)stream_);
-}
-
-int ryolo_conv2d_bn_act(const ryolo_conv_desc *d, const void *x, const void *w_packed, const float *scale,
-                        const float *shift, const void *residual, void *y, void *stream_) {
-    return ryolo_conv2d_bn_act_stats(d, x, w_packed, scale, shift, residual, y, nullptr, stream_);
+                                 a->slope, (hipStream_t)stream_);
 }
 
 int ryolo_conv0_recompute_supported(const ryolo_conv_desc *d) {
-    if (validate(d) != RYOLO_OK) return 0;
-    const long long M = (long long)d->N * d->H * d->W;
-    return d->ksize == 3 && d->stride == 1 && d->pad == 1 && d->Cin == 8 && d->in_cstride == 8 && d->Cout == 32 && d->upsample == 1 &&
-           !(d->tile & 0x1ff) && d->W >= 16 && M * 16 < 0x7fffff00ll && ((M - 1) * d->out_cstride + 32) * 2 < 0x7fffff00ll;
+    return conv_validate(d) == RYOLO_OK && conv0_shape(d, d->out_cstride) ? 1 : 0;
 }
 
 int ryolo_conv0_bn_act_fwd(const ryolo_conv_desc *d, const void *x, const void *w_packed, const float *scale, const float *shift,
@@ -1861,27 +1816,19 @@ int ryolo_conv0_bn_act_fwd(const ryolo_conv_desc *d, const void *x, const void *
     if (!ryolo_conv0_recompute_supported(d) || !x || !w_packed || !scale || !shift || !y) return RYOLO_EINVAL;
     if (act < 0 || act > 2 || (act == RYOLO_ACT_LEAKY && !slope)) return RYOLO_EINVAL;
     if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w_packed) & 15) return RYOLO_EINVAL;
-    ConvParams p;
-    p.x = (const __bf16 *)x; p.w = (const __bf16 *)w_packed; p.scale = scale; p.shift = shift; p.res = nullptr; p.y = (__bf16 *)y;
-    p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = 8; p.in_cs = 8; p.Ho = d->H; p.Wo = d->W; p.Cout = 32; p.out_cs = d->out_cstride; p.res_cs = 0;
-    p.stride = 1; p.pad = 1; p.K = 72; p.Kpad = (72 + BK - 1) / BK * BK;
-    p.M = (int)((long long)d->N * d->H * d->W);
-    p.act = act; p.slope = 0.f; p.ups = 1; p.stat_part = nullptr; p.stat_cpad = 0;
-    p.x_bytes = (unsigned)((unsigned long long)p.M * 16ull);
-    p.w_bytes = (unsigned)((((unsigned long long)p.M - 1) * d->out_cstride + 32) * 2ull);
-    p.nt_out = (long long)p.M * 64 >= nt_out_min_bytes() ? 1 : 0;
+    ConvParams p{};
+    const int gpw = 32;
+    unsigned nblk;
+    if (!conv0_params(d, d->out_cstride, p, gpw, &nblk)) return RYOLO_EINVAL;
+    p.x = (const __bf16 *)x; p.w = (const __bf16 *)w_packed; p.scale = scale; p.shift = shift; p.y = (__bf16 *)y;
+    p.act = act; p.slope = 0.f;
     C8Bwd bw;
     bw.slope = act == RYOLO_ACT_LEAKY ? slope : nullptr;
     bw.round_z = 1;
-    const long long groups = ((long long)p.M + 15) / 16;
-    const int gpw = 32;
-    const unsigned nblk = (unsigned)(((groups + gpw - 1) / gpw + 3) / 4);
-    hipStream_t stream = (hipStream_t)stream_;
-    if (conv0_halo_on()) return launch_conv0_halo(p, bw.slope, 1, cu_count(), stream);
-    if (act == RYOLO_ACT_LEAKY) hipLaunchKernelGGL((conv3x3_c8_direct_kernel<false, RYOLO_ACT_LEAKY, 0>), dim3(nblk), dim3(256), 0, stream, p, gpw, bw);
-    else if (act == RYOLO_ACT_MISH) hipLaunchKernelGGL((conv3x3_c8_direct_kernel<false, RYOLO_ACT_MISH, 0>), dim3(nblk), dim3(256), 0, stream, p, gpw, bw);
-    else hipLaunchKernelGGL((conv3x3_c8_direct_kernel<false, RYOLO_ACT_LINEAR, 0>), dim3(nblk), dim3(256), 0, stream, p, gpw, bw);
-    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+    ConvLaunch lc;
+    lc.stream = (hipStream_t)stream_;
+    if (conv0_halo_on()) return launch_conv0_halo(p, bw.slope, 1, lc);
+    return launch_c8_mode(act, p, gpw, nblk, bw, 0, lc.stream);
 }
 
 size_t ryolo_conv0_bn_bwd_workspace_bytes(void) { return (size_t)STAT_ROWS * 96 * 8 + 64 * 4; }
@@ -1897,675 +1844,25 @@ int ryolo_conv0_bn_bwd(const ryolo_conv_desc *d, const void *x, const void *w_pa
     if (act < 0 || act > 2 || (act == RYOLO_ACT_LEAKY && !slope)) return RYOLO_EINVAL;
     if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dz | (uintptr_t)w_packed | (uintptr_t)workspace) & 15) return RYOLO_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
-    ConvParams p;
-    p.x = (const __bf16 *)x; p.w = (const __bf16 *)w_packed; p.scale = scale; p.shift = shift; p.res = nullptr; p.y = (__bf16 *)dz;
-    p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = 8; p.in_cs = 8; p.Ho = d->H; p.Wo = d->W; p.Cout = 32; p.out_cs = dz_cstride; p.res_cs = 0;
-    p.stride = 1; p.pad = 1; p.K = 72; p.Kpad = (72 + BK - 1) / BK * BK;
-    p.M = (int)((long long)d->N * d->H * d->W);
-    p.act = act; p.ups = 1; p.stat_part = nullptr; p.stat_cpad = 0;
-    p.x_bytes = (unsigned)((unsigned long long)p.M * 16ull);
-    p.w_bytes = (unsigned)((((unsigned long long)p.M - 1) * dz_cstride + 32) * 2ull);        // the kernel's second descriptor covers dz
-    p.nt_out = (long long)p.M * 64 >= nt_out_min_bytes() ? 1 : 0;
-    p.slope = 0.f;
+    ConvParams p{};
+    const int gpw = 32;
+    unsigned nblk;
     C8Bwd bw;
+    if (!conv0_params(d, dz_cstride, p, gpw, &nblk) || !buffer_extent(p.M, dy_cstride, 32, &bw.dy_bytes)) return RYOLO_EINVAL;   // (the launch writes dz)
+    p.x = (const __bf16 *)x; p.w = (const __bf16 *)w_packed; p.scale = scale; p.shift = shift; p.y = (__bf16 *)dz;
+    p.act = act; p.slope = 0.f;
     bw.slope = act == RYOLO_ACT_LEAKY ? slope : nullptr;            // the learnable slope stays on the device
     bw.dy = (const __bf16 *)dy; bw.dy_cs = dy_cstride; bw.mean = mean;
-    bw.dy_bytes = (unsigned)((((unsigned long long)p.M - 1) * dy_cstride + 32) * 2ull);
     double *part = (double *)workspace;
     float *kb = (float *)(part + (size_t)STAT_ROWS * 96), *kd = kb + 32;
     bw.part = part; bw.kb = kb; bw.kd = kd;
     if (!workspace_is_zero && hipMemsetAsync(part, 0, (size_t)STAT_ROWS * 96 * 8, stream) != hipSuccess) return RYOLO_ELAUNCH;
-    const long long groups = ((long long)p.M + 15) / 16;
-    const int gpw = 32;
-    const unsigned nblk = (unsigned)(((groups + gpw - 1) / gpw + 3) / 4);
-    int rc;
-#define C8_BWD(MODE_)                                                                                                      \
-    rc = act == RYOLO_ACT_LEAKY ? launch_c8_bwd<RYOLO_ACT_LEAKY>(p, gpw, nblk, bw, MODE_, stream)                          \
-         : (act == RYOLO_ACT_MISH ? launch_c8_bwd<RYOLO_ACT_MISH>(p, gpw, nblk, bw, MODE_, stream)                          \
-                                  : launch_c8_bwd<RYOLO_ACT_LINEAR>(p, gpw, nblk, bw, MODE_, stream));
-    C8_BWD(2)
+    int rc = launch_c8_mode(act, p, gpw, nblk, bw, 2, stream);
     if (rc != RYOLO_OK) return rc;
-    hipLaunchKernelGGL(conv0_bwd_finalize_kernel, dim3(1), dim3(32), 0, stream, part, scale, mean, invstd, 1.0f / (float)p.M, kb, kd,
-                       dgamma, dbeta, act == RYOLO_ACT_LEAKY ? dslope : nullptr);
-    C8_BWD(3)
-#undef C8_BWD
-    return rc;
-}
-
-int ryolo_conv_kernel_choice(const ryolo_conv_desc *d, int with_residual, int with_statistics) {
-    int choice = -1;
-    g_conv_choice = &choice;
-    void *fake = (void *)(uintptr_t)4096;      // never dereferenced: the dispatch returns before any launch
-    const int rc = ryolo_conv2d_bn_act_stats(d, fake, fake, (const float *)fake, (const float *)fake, with_residual ? fake : nullptr, fake,
-                                             with_statistics ? (double *)fake : nullptr, nullptr);
-    g_conv_choice = nullptr;
-    return rc == RYOLO_OK ? choice : -1;
-}
-
-static int bnreduce_plan(const ryolo_conv_desc *d, int *mode);
-
-int ryolo_conv_dgrad_kernel_choice(const ryolo_conv_desc *d, int with_bn_reduce) {
-    int choice = -1;
-    void *fake = (void *)(uintptr_t)4096;      // never dereferenced: the dispatch returns before any launch
-    BnRed br{};
-    int mode = 0;
-    if (with_bn_reduce) {                      // ryolo_conv2d_dgrad_bnreduce: the kernel its plan picks
-        if (!bnreduce_plan(d, &mode)) return -1;
-        g_bnred = &br;
-        g_bnred_mode = mode;
-    }
-    g_conv_choice = &choice;
-    const int rc = ryolo_conv2d_dgrad(d, fake, d ? d->Cout : 0, fake, (const float *)fake, (const float *)fake, fake, 1, nullptr);
-    g_conv_choice = nullptr;
-    g_bnred = nullptr;
-    return rc == RYOLO_OK ? choice : -1;
-}
-
-// ------------------------------------------------------------------------------------------------ dgrad
-// dx[n, hi, wi, ci] (+)= sum_{kh,kw,co} dz[n, ho, wo, co] * W[co, ci, kh, kw],  ho*s - pad + kh = hi (same for w).
-// stride 1: a plain convolution of dz with the spatially flipped, channel-transposed filter.
-// stride 2 (3x3, pad 1): four output-parity classes (hi%2, wi%2) = (a, b); class (a, b) only sees the taps with
-// kh = a+1 (mod 2), kw = b+1 (mod 2) -> 1, 2, 2 or 4 taps, each a stride-1 gather dz[(hi+1-kh)/2, (wi+1-kw)/2];
-// each class is one launch of the same kernel with its own tap list, packed filter and strided output placement.
-static int dgrad_classes(int ks, int stride, int pad, int cls, int *dy, int *dx, int *khs, int *kws) {
-    // returns ntaps of class `cls` (stride 1: cls must be 0); tap t reads dz pixel (i + dy[t], j + dx[t]) * of the class grid
-    if (stride == 1) {
-        int n = 0;
-        for (int kh = 0; kh < ks; kh++)
-            for (int kw = 0; kw < ks; kw++) {   // dz pixel = hi + pad - kh' where kh' runs over the flipped filter
-                dy[n] = kh; dx[n] = kw; khs[n] = ks - 1 - kh; kws[n] = ks - 1 - kw;
-                n++;
-            }
-        return n;
-    }
-    const int a = cls >> 1, b = cls & 1;
-    int n = 0;
-    for (int kh = ks - 1; kh >= 0; kh--) {
-        if (((a + pad - kh) & 1) != 0) continue;
-        for (int kw = ks - 1; kw >= 0; kw--) {
-            if (((b + pad - kw) & 1) != 0) continue;
-            // hi = 2i + a -> ho = (2i + a + pad - kh) / 2 = i + (a + pad - kh) / 2
-            dy[n] = (a + pad - kh) / 2; dx[n] = (b + pad - kw) / 2; khs[n] = kh; kws[n] = kw;
-            n++;
-        }
-    }
-    return n;
-}
-
-// x-fused stride-2 classes (3x3, pad 1, C_in a multiple of 32 and <= 64 -- the stem, where one input pixel is only 64-128 B):
-// the two column parities of a row parity `a` become ONE launch whose output "pixel" (i, j) is the pair of input pixels
-// (2i+a, 2j), (2i+a, 2j+1) = 2*C_in contiguous channels, so a store writes whole lines and dz is read twice, not four times.
-// Taps (kh, dxo in {0,1}) read dz pixel (i + dy, j + dxo); the weight of output half b at a tap is the filter column
-// b == 0 ? (dxo == 0 ? 1 : none) : (dxo == 0 ? 2 : 0).
-static inline bool dgrad_xfusable(int Cout, int Cin, int ksize, int stride) {
-    (void)Cout;
-    return stride == 2 && ksize == 3 && Cin <= 64 && Cin % 32 == 0;
-}
-static int dgrad_xfused_class(int a, int *dy, int *dx, int *khs, int *kw0, int *kw1) {
-    int n = 0;
-    for (int kh = 2; kh >= 0; kh--) {
-        if (((a + 1 - kh) & 1) != 0) continue;
-        for (int dxo = 0; dxo < 2; dxo++) {
-            dy[n] = (a + 1 - kh) / 2; dx[n] = dxo; khs[n] = kh;
-            kw0[n] = dxo == 0 ? 1 : -1;
-            kw1[n] = dxo == 0 ? 2 : 0;
-            n++;
-        }
-    }
-    return n;
-}
-static size_t dgrad_classic_bytes(int Cout, int Cin, int ksize, int stride) {
-    const size_t rows = ((size_t)Cin + 127) / 128 * 128;
-    size_t total = 0;
-    int dy[9], dx[9], khs[9], kws[9];
-    for (int cls = 0; cls < (stride == 1 ? 1 : 4); cls++) {
-        const int nt = dgrad_classes(ksize, stride, (ksize - 1) / 2, cls, dy, dx, khs, kws);
-        const size_t Kpad = ((size_t)nt * Cout + BK - 1) / BK * BK;
-        total += (rows * Kpad + 128) * 2;
-    }
-    return total;
-}
-
-size_t ryolo_conv_packed_dgrad_bytes(int Cout, int Cin, int ksize, int stride) {
-    if (Cout <= 0 || Cin <= 0 || (ksize != 1 && ksize != 3) || (stride != 1 && stride != 2)) return 0;
-    size_t total = dgrad_classic_bytes(Cout, Cin, ksize, stride);
-    if (dgrad_xfusable(Cout, Cin, ksize, stride)) {       // the x-fused images follow the four classic ones
-        const size_t rows = ((size_t)2 * Cin + 127) / 128 * 128;
-        int dy[9], dx[9], khs[9], k0[9], k1[9];
-        for (int a = 0; a < 2; a++) {
-            const int nt = dgrad_xfused_class(a, dy, dx, khs, k0, k1);
-            const size_t Kpad = ((size_t)nt * Cout + BK - 1) / BK * BK;
-            total += (rows * Kpad + 128) * 2;
-        }
-    }
-    return total;
-}
-
-struct XfTaps { int khs[9], kw0[9], kw1[9]; };
-__global__ void pack_dgrad_xfused_kernel(const float *__restrict__ w, int Cout, int Cin, int ntaps, XfTaps tp, int Kpad, int rows,
-                                         __bf16 *__restrict__ out) {
-    // out[b*Cin + ci][t*Cout + co] = w[co][ci][kh_t][kw_{b,t}] (0 where the half has no column at that tap)
-    const size_t total = (size_t)rows * Kpad + 128;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        float v = 0.f;
-        if (i < (size_t)rows * Kpad) {
-            const int rr = (int)(i / Kpad), k = (int)(i % Kpad);
-            const int t = k / Cout, co = k % Cout;
-            if (rr < 2 * Cin && t < ntaps) {
-                const int b = rr / Cin, ci = rr - b * Cin;
-                const int kw = b ? tp.kw1[t] : tp.kw0[t];
-                if (kw >= 0) v = w[(((size_t)co * Cin + ci) * 3 + tp.khs[t]) * 3 + kw];
-            }
-        }
-        out[i] = (__bf16)v;
-    }
-}
-
-__global__ void pack_dgrad_kernel(const float *__restrict__ w, int Cout, int Cin, int KS, int ntaps, const int *khs_kws,
-                                  int Kpad, int rows, __bf16 *__restrict__ out) {
-    // out[ci][t*Cout + co] = w[co][ci][kh_t][kw_t]
-    const size_t total = (size_t)rows * Kpad + 128;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        float v = 0.f;
-        if (i < (size_t)rows * Kpad) {
-            const int ci = (int)(i / Kpad), k = (int)(i % Kpad);
-            const int t = k / Cout, co = k % Cout;
-            if (ci < Cin && t < ntaps) v = w[(((size_t)co * Cin + ci) * KS + khs_kws[t]) * KS + khs_kws[9 + t]];
-        }
-        out[i] = (__bf16)v;
-    }
-}
-
-// ---- all weight packs of a training step in ONE launch (forward layout + every dgrad class of every conv) ----------
-// 160 small launches per step otherwise (1.1 ms of launch-bound time at bs 32).  `jobs` is a device array built once by
-// the caller with ryolo_conv_pack_job_fill; workgroup b serves the job whose [block_begin, block_end) contains b.
-constexpr int PK_ROWS = 4;            // forward layout: output rows (c_out) per workgroup
-constexpr int PK_CI = 32, PK_CO = 64;  // dgrad layout: (c_in rows) x (c_out columns) per workgroup
-constexpr int PK_PAD = 2;             // dgrad sub-block: bf16 elements added to each c_out's run in LDS.  The transposing read walks c_out
-                                      // across the lanes; 288 elements = 144 words per run put 64 lanes on 4 banks (16-way conflict),
-                                      // 145 words spread them over all 64
-constexpr int PK_UB = 6;              // 16-B loads a thread keeps in flight while it stages a tile (one per trip left the pass latency-bound)
-constexpr int PK_LDS = PK_CO * (PK_CI * 9 + PK_PAD);   // bf16 elements: one [64 c_out][32 c_in][9 taps] sub-block, or one forward row
-__global__ void __launch_bounds__(256) pack_batch_kernel(const ryolo_pack_job *__restrict__ jobs, int njobs) {
-    // Both layouts are transposes of the OIHW parameter, so each workgroup moves a TILE through LDS: it reads the fp32
-    // source in its own order (whole [c_in][taps] rows / 32-channel runs of them: coalesced) and writes bf16 runs that are
-    // contiguous in the destination.  The element-wise gather this replaces read the 250 MB of weights through 36-byte
-    // (forward) and 4.6-KB (dgrad) strides: 0.92 ms per step.
-    __shared__ __bf16 sm[PK_LDS];
-    int lo = 0;                             // last job with block_begin <= blockIdx.x (block_begin ascending, jobs[0] starts at 0)
-    if (njobs <= 256) {                     // one round of parallel loads + a count, not eight dependent loads of a binary search
-        lo = __syncthreads_count((int)threadIdx.x < njobs && jobs[threadIdx.x].block_begin <= (int)blockIdx.x) - 1;
-    } else {
-        int hi = njobs - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (jobs[mid].block_begin <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-        }
-    }
-    const ryolo_pack_job j = jobs[lo];
-    const int blk = (int)blockIdx.x - j.block_begin;
-    const float *__restrict__ w = (const float *)j.src;
-    __bf16 *__restrict__ out = (__bf16 *)j.dst;
-    const int KK = j.KS * j.KS;
-    const int tid = threadIdx.x;
-    if (blk == 0)                           // the 128-element zero page behind the body
-        for (int i = tid; i < 128; i += 256) out[(size_t)j.rows * j.Kpad + i] = (__bf16)0.f;
-    if (j.kind == 0) {                      // forward: out[co][tap*Cin_pad + c] = w[co][c][tap]
-        const int rowlen = j.Cin * KK;
-        const int rl4 = (rowlen + 3) & ~3;                       // a row's slot in LDS (8-B aligned)
-        const int fit = PK_LDS / rl4 < PK_ROWS ? (PK_LDS / rl4 < 1 ? 1 : PK_LDS / rl4) : PK_ROWS;   // rows staged together: one load
-        for (int rr0 = 0; rr0 < PK_ROWS; rr0 += fit) {           // round and one barrier pair for all of them when they fit
-            const int rbase = blk * PK_ROWS + rr0;
-            if (rbase >= j.rows) break;
-            for (int rr = 0; rr < fit && rr0 + rr < PK_ROWS; rr++) {
-                const int r = rbase + rr;
-                if (r >= j.Cout) break;                          // (rows past C_out are zero rows: nothing to stage)
-                __bf16 *dst = sm + rr * rl4;
-                if ((rowlen & 3) == 0 && ((uintptr_t)w & 15) == 0) {    // 16-B loads (a row starts at a multiple of 4 floats then, and the parameter itself at a
-                                                                        // 16-B boundary: a view into a flat buffer may not -- those take the scalar path)
-                    const float4 *w4 = (const float4 *)(w + (size_t)r * rowlen);
-                    for (int i0 = tid; i0 < rowlen / 4; i0 += 256 * PK_UB) {     // PK_UB independent loads in flight per thread
-                        float4 v[PK_UB];
-#pragma unroll
-                        for (int u = 0; u < PK_UB; u++)
-                            if (i0 + u * 256 < rowlen / 4) v[u] = w4[i0 + u * 256];
-#pragma unroll
-                        for (int u = 0; u < PK_UB; u++) {
-                            if (i0 + u * 256 >= rowlen / 4) break;
-                            bf16x4 o;
-                            o[0] = (__bf16)v[u].x; o[1] = (__bf16)v[u].y; o[2] = (__bf16)v[u].z; o[3] = (__bf16)v[u].w;
-                            *(bf16x4 *)(dst + 4 * (i0 + u * 256)) = o;
-                        }
-                    }
-                } else {
-                    for (int i = tid; i < rowlen; i += 256) dst[i] = (__bf16)w[(size_t)r * rowlen + i];
-                }
-            }
-            __syncthreads();
-            for (int rr = 0; rr < fit && rr0 + rr < PK_ROWS; rr++) {
-                const int r = rbase + rr;
-                if (r >= j.rows) break;
-                const bool real = r < j.Cout;
-                const __bf16 *src = sm + rr * rl4;
-                if ((j.Cin_pad & 7) == 0) {     // 8 consecutive k share a tap: one 16-B store per thread and trip (Kpad % 64 == 0)
-                    for (int k8 = tid * 8; k8 < j.Kpad; k8 += 256 * 8) {
-                        const int tap = k8 / j.Cin_pad, c0 = k8 - tap * j.Cin_pad;
-                        bf16x8 v;
-#pragma unroll
-                        for (int e = 0; e < 8; e++) v[e] = (real && tap < KK && c0 + e < j.Cin) ? src[(c0 + e) * KK + tap] : (__bf16)0.f;
-                        *(bf16x8 *)(out + (size_t)r * j.Kpad + k8) = v;
-                    }
-                } else {
-                    for (int k = tid; k < j.Kpad; k += 256) {
-                        const int tap = k / j.Cin_pad, c = k - tap * j.Cin_pad;
-                        out[(size_t)r * j.Kpad + k] = (real && tap < KK && c < j.Cin) ? src[c * KK + tap] : (__bf16)0.f;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-        return;
-    }
-    // dgrad class: out[ci][t*Cout + co] = w[co][ci][kh_t][kw_t]; kind 2 (x-fused stride-2 class): rows are (b, ci), the
-    // filter column of tap t is nibble b of kws[t] minus 1 (-1: this half has no column there)
-    const int cob = (j.Cout + PK_CO - 1) / PK_CO;
-    const int row0 = (blk / cob) * PK_CI, co0 = (blk % cob) * PK_CO;
-    const int half = (j.kind == 2 && row0 >= j.Cin) ? 1 : 0;
-    const int ci0 = j.kind == 2 ? row0 - half * j.Cin : row0;
-    const bool live = j.kind != 2 || row0 < 2 * j.Cin;
-    const int run = PK_CI * KK;             // one c_out's share of the sub-block: 32 c_in x taps, contiguous in w
-    const int pitch = run + PK_PAD;
-    if ((run & 3) == 0 && (j.Cin & 3) == 0 && ci0 + PK_CI <= j.Cin && ((uintptr_t)w & 15) == 0) {
-        // whole 32-channel runs: 16-B loads (a run starts at (co * Cin + ci0) * KK floats, a multiple of 4); the LDS pitch is odd in
-        // words, so the four bf16 go out as two 4-B stores
-        static_assert((PK_CI * 9 + PK_PAD) % 2 == 0, "4-B aligned runs in LDS");
-        const int run4 = run / 4;
-        for (int i0 = tid; i0 < PK_CO * run4; i0 += 256 * PK_UB) {       // PK_UB independent loads in flight per thread
-            float4 v[PK_UB];
-#pragma unroll
-            for (int u = 0; u < PK_UB; u++) {
-                const int i = i0 + u * 256;
-                const int col = i / run4, q = i - col * run4;
-                v[u] = float4{0.f, 0.f, 0.f, 0.f};
-                if (i < PK_CO * run4 && live && co0 + col < j.Cout) v[u] = *(const float4 *)(w + ((size_t)(co0 + col) * j.Cin + ci0) * KK + 4 * q);
-            }
-#pragma unroll
-            for (int u = 0; u < PK_UB; u++) {
-                const int i = i0 + u * 256;
-                if (i >= PK_CO * run4) break;
-                const int col = i / run4, q = i - col * run4;
-                bf16x2 lo, hi;
-                lo[0] = (__bf16)v[u].x; lo[1] = (__bf16)v[u].y; hi[0] = (__bf16)v[u].z; hi[1] = (__bf16)v[u].w;
-                *(bf16x2 *)(sm + col * pitch + 4 * q) = lo;
-                *(bf16x2 *)(sm + col * pitch + 4 * q + 2) = hi;
-            }
-        }
-    } else {
-        for (int i = tid; i < PK_CO * run; i += 256) {
-            const int col = i / run, rem = i - col * run;
-            const int co = co0 + col, ci = ci0 + rem / KK;
-            sm[col * pitch + rem] = (live && co < j.Cout && ci < j.Cin) ? (__bf16)w[((size_t)co * j.Cin + ci0) * KK + rem] : (__bf16)0.f;
-        }
-    }
-    __syncthreads();
-    if ((j.Cout & 7) == 0) {                // 8 consecutive c_out per thread: 16-B stores (every row offset is a multiple of 8 elements)
-        for (int i = tid; i < PK_CI * j.ntaps * (PK_CO / 8); i += 256) {
-            const int col = (i % (PK_CO / 8)) * 8, t = (i / (PK_CO / 8)) % j.ntaps, cil = i / ((PK_CO / 8) * j.ntaps);
-            if (co0 + col < j.Cout) {
-                const int kw = j.kind == 2 ? ((j.kws[t] >> (4 * half)) & 15) - 1 : j.kws[t];
-                const int src = cil * KK + j.khs[t] * j.KS + kw;
-                bf16x8 v;
-#pragma unroll
-                for (int e = 0; e < 8; e++) v[e] = kw >= 0 ? sm[(col + e) * pitch + src] : (__bf16)0.f;
-                *(bf16x8 *)(out + (size_t)(row0 + cil) * j.Kpad + t * j.Cout + co0 + col) = v;
-            }
-        }
-    } else {
-        for (int i = tid; i < PK_CI * j.ntaps * PK_CO; i += 256) {
-            const int col = i % PK_CO, t = (i / PK_CO) % j.ntaps, cil = i / (PK_CO * j.ntaps);
-            if (co0 + col < j.Cout) {
-                const int kw = j.kind == 2 ? ((j.kws[t] >> (4 * half)) & 15) - 1 : j.kws[t];
-                out[(size_t)(row0 + cil) * j.Kpad + t * j.Cout + co0 + col] =
-                    kw >= 0 ? sm[col * pitch + cil * KK + j.khs[t] * j.KS + kw] : (__bf16)0.f;
-            }
-        }
-    }
-    if (co0 == 0) {                         // K padding behind the last tap of these 32 rows
-        const int kreal = j.ntaps * j.Cout, padn = j.Kpad - kreal;
-        for (int i = tid; i < PK_CI * padn; i += 256) out[(size_t)(row0 + i / padn) * j.Kpad + kreal + i % padn] = (__bf16)0.f;
-    }
-}
-
-int ryolo_conv_pack_job_fill(ryolo_pack_job *host_jobs /* room for 7 */, const float *w_oihw, int Cout, int Cin, int ksize,
-                             int stride, int Cin_pad, void *packed_fwd, void *packed_dgrad /* or NULL */) {
-    if (!host_jobs || !w_oihw || !packed_fwd || Cout <= 0 || Cin <= 0 || Cin_pad < Cin || (ksize != 1 && ksize != 3) ||
-        (stride != 1 && stride != 2))
-        return -1;
-    int n = 0;
-    {
-        ryolo_pack_job &j = host_jobs[n++];
-        j = ryolo_pack_job{};
-        j.src = w_oihw; j.dst = packed_fwd; j.kind = 0; j.Cout = Cout; j.Cin = Cin; j.KS = ksize; j.Cin_pad = Cin_pad;
-        j.Kpad = (ksize * ksize * Cin_pad + BK - 1) / BK * BK;
-        j.rows = (Cout + 127) / 128 * 128;
-        j.block_begin = 0; j.block_end = (j.rows + PK_ROWS - 1) / PK_ROWS;      // workgroups of pack_batch_kernel
-        if (Cin * ksize * ksize > PK_LDS) return -1;
-    }
-    if (packed_dgrad) {
-        if (ryolo_conv_packed_dgrad_bytes(Cout, Cin, ksize, stride) == 0) return -1;
-        char *dst = (char *)packed_dgrad;
-        for (int cls = 0; cls < (stride == 1 ? 1 : 4); cls++) {
-            int dy[9], dx[9], khs[9], kws[9];
-            const int nt = dgrad_classes(ksize, stride, (ksize - 1) / 2, cls, dy, dx, khs, kws);
-            ryolo_pack_job &j = host_jobs[n++];
-            j = ryolo_pack_job{};
-            j.src = w_oihw; j.dst = dst; j.kind = 1; j.Cout = Cout; j.Cin = Cin; j.KS = ksize; j.ntaps = nt;
-            for (int t = 0; t < nt; t++) { j.khs[t] = khs[t]; j.kws[t] = kws[t]; }
-            j.Kpad = (nt * Cout + BK - 1) / BK * BK;
-            j.rows = (Cin + 127) / 128 * 128;
-            j.block_begin = 0; j.block_end = (j.rows / PK_CI) * ((Cout + PK_CO - 1) / PK_CO);
-            dst += ((size_t)j.rows * j.Kpad + 128) * 2;
-        }
-        if (dgrad_xfusable(Cout, Cin, ksize, stride)) {
-            for (int a = 0; a < 2; a++) {
-                int dy[9], dx[9], khs[9], k0[9], k1[9];
-                const int nt = dgrad_xfused_class(a, dy, dx, khs, k0, k1);
-                ryolo_pack_job &j = host_jobs[n++];
-                j = ryolo_pack_job{};
-                j.src = w_oihw; j.dst = dst; j.kind = 2; j.Cout = Cout; j.Cin = Cin; j.KS = ksize; j.ntaps = nt;
-                for (int t = 0; t < nt; t++) { j.khs[t] = khs[t]; j.kws[t] = (k0[t] + 1) | ((k1[t] + 1) << 4); }
-                j.Kpad = (nt * Cout + BK - 1) / BK * BK;
-                j.rows = (2 * Cin + 127) / 128 * 128;
-                j.block_begin = 0; j.block_end = (j.rows / PK_CI) * ((Cout + PK_CO - 1) / PK_CO);
-                dst += ((size_t)j.rows * j.Kpad + 128) * 2;
-            }
-        }
-    }
-    return n;
-}
-
-int ryolo_conv_pack_batch(const ryolo_pack_job *device_jobs, int njobs, int total_blocks, void *stream) {
-    if (!device_jobs || njobs <= 0 || total_blocks <= 0) return RYOLO_EINVAL;
-    hipLaunchKernelGGL(pack_batch_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, device_jobs, njobs);
-    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
-}
-
-int ryolo_conv_dgrad_tap_table(int ksize, int stride, int *host_out /* int[72] */) {
-    if (!host_out || (ksize != 1 && ksize != 3) || (stride != 1 && stride != 2)) return RYOLO_EINVAL;
-    for (int i = 0; i < 72; i++) host_out[i] = 0;
-    for (int cls = 0; cls < (stride == 1 ? 1 : 4); cls++) {
-        int dy[9], dx[9];
-        dgrad_classes(ksize, stride, (ksize - 1) / 2, cls, dy, dx, host_out + cls * 18, host_out + cls * 18 + 9);
-    }
-    return RYOLO_OK;
-}
-
-int ryolo_conv_pack_weights_dgrad(const float *w_oihw, int Cout, int Cin, int ksize, int stride, void *packed,
-                                  const int *taps_table /* device int[72] from ryolo_conv_dgrad_tap_table */, void *stream_) {
-    if (!w_oihw || !packed || !taps_table || ryolo_conv_packed_dgrad_bytes(Cout, Cin, ksize, stride) == 0) return RYOLO_EINVAL;
-    hipStream_t stream = (hipStream_t)stream_;
-    const int rows = (Cin + 127) / 128 * 128;
-    char *dst = (char *)packed;
-    for (int cls = 0; cls < (stride == 1 ? 1 : 4); cls++) {
-        int dy[9], dx[9], kk[18];
-        const int nt = dgrad_classes(ksize, stride, (ksize - 1) / 2, cls, dy, dx, kk, kk + 9);
-        const int Kpad = (nt * Cout + BK - 1) / BK * BK;
-        const size_t total = (size_t)rows * Kpad + 128;
-        const int nb = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        hipLaunchKernelGGL(pack_dgrad_kernel, dim3(nb), dim3(256), 0, stream, w_oihw, Cout, Cin, ksize, nt,
-                           taps_table + cls * 18, Kpad, rows, (__bf16 *)dst);
-        dst += total * 2;
-    }
-    if (dgrad_xfusable(Cout, Cin, ksize, stride)) {
-        const int rows2 = (2 * Cin + 127) / 128 * 128;
-        for (int a = 0; a < 2; a++) {
-            int dy[9], dx[9];
-            XfTaps tp;
-            const int nt = dgrad_xfused_class(a, dy, dx, tp.khs, tp.kw0, tp.kw1);
-            for (int t = nt; t < 9; t++) { tp.khs[t] = 0; tp.kw0[t] = -1; tp.kw1[t] = -1; }
-            const int Kpad = (nt * Cout + BK - 1) / BK * BK;
-            const size_t total = (size_t)rows2 * Kpad + 128;
-            const int nb = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-            hipLaunchKernelGGL(pack_dgrad_xfused_kernel, dim3(nb), dim3(256), 0, stream, w_oihw, Cout, Cin, nt, tp, Kpad, rows2,
-                               (__bf16 *)dst);
-            dst += total * 2;
-        }
-    }
-    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
-}
-
-// rows of partial sums (= workgroups of the persistent grid) the fused launch writes, 0 when this conv's data gradient cannot carry
-// the reduce: 1x1 stride 1, whole 128-channel tiles on both sides, dense input gradient, a tile list deep enough for the
-// persistent kernel (the same tests dispatch() / launch_variant() apply)
-// rows of partial sums and which kernel carries the reduce.  conv_pw.hip where it is the faster data gradient (K = 128: the 76^2
-// residual blocks, 127 vs 133 us at bs 64) and where the persistent 128 x 128 tile does not apply (tile lists less than 2.5 rounds
-// deep: 19^2); the persistent tile elsewhere (38^2: 68 vs 70 us, 19^2 K 512: 49 vs 54 us; tools/pw_bench.py --train).
-// Mode 3 of the plan below: the stride-1 data gradients whose natural kernel is one of the one-tile-per-workgroup / narrow tiles (the
-// 3x3 layers with C_in <= 128, the 1x1 layers with C_in <= 64).  Two dry runs of the dispatch decide: the kernel the plain data gradient
-// takes must be one of those tiles (a layer that conv_mq / conv_mp serve keeps them: the reduce is not worth a slower conv), and the launch
-// with the reduce must exist.  Returns the rows (= pixel tiles) or 0.
-static int bnreduce_plan_tiles(const ryolo_conv_desc *d) {
-    if (d->stride != 1 || (d->tile & 0xff) || d->in_cstride != d->Cin || (d->Cin & 7)) return 0;
-    int knob = 1;
-    {   // RYOLO_BN_REDUCE_TILES = 0: off (A/B timing; ryolo_set_tuning)
-        const char *e = tune(TUNE_BN_REDUCE_TILES);
-        if (e) knob = atoi(e);
-        if (knob == 0) return 0;
-    }
-    void *fake = (void *)(uintptr_t)4096;      // never dereferenced: the dispatch returns before any launch
-    const BnRed *sv_b = g_bnred;
-    const int sv_m = g_bnred_mode;
-    int *sv_c = g_conv_choice;
-    BnRed br{};
-    int natural = -1, fused = -1;
-    g_bnred = nullptr;
-    g_conv_choice = &natural;
-    int rc = ryolo_conv2d_dgrad(d, fake, d->Cout, fake, (const float *)fake, (const float *)fake, fake, 1, nullptr);
-    if (rc == RYOLO_OK) {
-        g_bnred = &br;
-        g_bnred_mode = 3;
-        g_conv_choice = &fused;
-        rc = ryolo_conv2d_dgrad(d, fake, d->Cout, fake, (const float *)fake, (const float *)fake, fake, 1, nullptr);
-    }
-    g_bnred = sv_b;
-    g_bnred_mode = sv_m;
-    g_conv_choice = sv_c;
-    if (rc != RYOLO_OK || natural != fused) return 0;
-    const int tile = fused - RYOLO_CONV_KERNEL_IGEMM;
-    const int bm = tile == 1 ? 128 : ((tile == 2 || tile == 3) ? 256 : 0);
-    if (!bm) return 0;
-    if (tile == 3) return 0;           // 256 x 32: the plain data gradient runs on the persistent grid (short K), 233 us faster than this launch
-    if (tile == 1 && knob == 2) return 0;
-    const long long M = (long long)d->N * d->H * d->W;
-    return (int)((M + bm - 1) / bm);
-}
-
-// mode 4: the data gradient's natural kernel is one of conv_mq.hip's 128-channel tiles -- the reduce rides in its epilogue, one row per
-// workgroup.  Returns the rows (= workgroups of that launch) or 0.
-static int bnreduce_plan_mq128(const ryolo_conv_desc *d) {
-    if (d->stride != 1 || (d->tile & 0xff) || d->in_cstride != d->Cin || (d->Cin & 127) || mq128_knob() <= 0) return 0;
-    void *fake = (void *)(uintptr_t)4096;      // never dereferenced: the dispatch returns before any launch
-    const BnRed *sv_b = g_bnred;
-    int *sv_c = g_conv_choice;
-    int natural = -1;
-    g_bnred = nullptr;
-    g_conv_choice = &natural;
-    const int rc = ryolo_conv2d_dgrad(d, fake, d->Cout, fake, (const float *)fake, (const float *)fake, fake, 1, nullptr);
-    g_bnred = sv_b;
-    g_conv_choice = sv_c;
-    if (rc != RYOLO_OK || (natural != RYOLO_CONV_KERNEL_MQ128 && natural != RYOLO_CONV_KERNEL_MQ64)) return 0;
-    ConvParams q;
-    q.M = (int)((long long)d->N * d->H * d->W);
-    q.Cout = d->Cin;
-    return conv_mq128_grid(q, natural == RYOLO_CONV_KERNEL_MQ128 ? 128 : 64);
-}
-
-static int bnreduce_plan(const ryolo_conv_desc *d, int *mode) {
-    *mode = 0;
-    if (validate(d) != RYOLO_OK) return 0;
-    {
-        const int r = bnreduce_plan_mq128(d);
-        if (r > 0) {
-            *mode = 4;
-            return r;
-        }
-    }
-    auto tiles = [&]() {
-        const int r = bnreduce_plan_tiles(d);
-        if (r > 0) *mode = 3;
-        return r;
-    };
-    if (d->ksize != 1 || d->stride != 1 || d->pad != 0) return tiles();
-    if ((d->Cin & 127) || (d->Cout & 63) || (d->tile & 0xff)) return tiles();
-    const long long M = (long long)d->N * d->H * d->W;
-    int g_pw = 0;
-    {   // the data gradient as conv_pw.hip sees it (K = the forward's C_out, channels = its C_in): its grid when it serves the shape
-        ConvParams q;
-        q.Cin = d->Cout; q.Kpad = (d->Cout + BK - 1) / BK * BK; q.Cout = d->Cin; q.pw_grid_cap = 0;
-        const int g = conv_pw_disabled() ? 0 : conv_pw_grid(q);
-        if (g > 0 && d->in_cstride == d->Cin && ((unsigned long long)(M + 1024 * 128) * d->Cout) * 2ull < 0x7fffff00ull &&
-            ((unsigned long long)M * d->Cin) * 2ull < 0x7fffff00ull)
-            g_pw = g;
-    }
-    const long long mt = (M + 127) / 128, nt = d->Cin / 128, T = mt * nt;
-    const int grid = (2 * cu_count()) & ~7;
-    const long long dmax = d->W > d->H ? d->W : d->H;
-    const bool persist_ok = !(grid < 8 || 2 * T < 5 * (long long)grid || mt * 128 * dmax >= 0x100000000ll || T * nt >= 0x100000000ll) &&
-                            ((unsigned long long)M * d->Cout) * 2ull < 0x7fffff00ull;
-    if (g_pw > 0 && (d->Cout == 128 || !persist_ok)) {
-        *mode = 1;
-        return g_pw;
-    }
-    if (persist_ok) {
-        *mode = 2;
-        return grid;
-    }
-    return tiles();
-}
-
-// rows of partial sums the fused launch writes (= workgroups of a persistent launch, pixel tiles of a one-tile-per-workgroup launch), 0 when
-// this conv's data gradient cannot carry the reduce: stride 1, dense input gradient, and one of the kernels with the folded pass (the
-// persistent 2x2 tile / conv_pw.hip for 1x1 layers with whole 128-channel tiles, the narrow and the 128 x 128 one-tile kernels otherwise)
-int ryolo_conv2d_dgrad_bnreduce_rows(const ryolo_conv_desc *d) {
-    int mode;
-    return bnreduce_plan(d, &mode);
-}
-
-int ryolo_conv2d_dgrad_bnreduce(const ryolo_conv_desc *d, const void *dz, int dz_cstride, const void *packed_dgrad, const float *ones,
-                                const float *zeros, void *dx, int accumulate, const void *z, int z_cstride, const float *scale,
-                                const float *shift, const float *mean, const float *invstd, const float *slope, float *part,
-                                void *stream_) {
-    int mode = 0;
-    if (!bnreduce_plan(d, &mode) || !z || (z_cstride & 7) || z_cstride < d->Cin || !scale || !shift || !mean || !invstd ||
-        !slope || !part || d->in_cstride != d->Cin)
-        return RYOLO_EINVAL;
-    BnRed br;
-    br.z = (const __bf16 *)z; br.z_cs = z_cstride; br.scale = scale; br.shift = shift; br.mean = mean; br.invstd = invstd;
-    br.slope = slope; br.part = part;
-    g_bnred = &br;
-    g_bnred_mode = mode;
-    const int rc = ryolo_conv2d_dgrad(d, dz, dz_cstride, packed_dgrad, ones, zeros, dx, accumulate, stream_);
-    g_bnred = nullptr;
-    return rc;
-}
-
-int ryolo_conv2d_dgrad(const ryolo_conv_desc *d /* the FORWARD conv */, const void *dz, int dz_cstride,
-                       const void *packed_dgrad, const float *ones, const float *zeros, void *dx, int accumulate,
-                       void *stream_) {
-    if (validate(d) != RYOLO_OK || !dz || !packed_dgrad || !ones || !zeros || !dx) return RYOLO_EINVAL;
-    if (d->stride != 1 && !(d->stride == 2 && d->ksize == 3 && d->pad == 1)) return RYOLO_EINVAL;
-    if ((dz_cstride & 7) || dz_cstride < d->Cout) return RYOLO_EINVAL;
-    const int Ho = (d->H + 2 * d->pad - d->ksize) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->ksize) / d->stride + 1;
-    const int rows = (d->Cin + 127) / 128 * 128;
-    const char *wsrc = (const char *)packed_dgrad;
-    // x-fused stride-2 classes when the input gradient is dense and its rows hold an even number of pixels (tile bit 0x8000
-    // forces the four classic classes: tests / A-B)
-    const bool xfuse = dgrad_xfusable(d->Cout, d->Cin, d->ksize, d->stride) && d->pad == 1 && (d->W & 1) == 0 &&
-                       d->in_cstride == d->Cin && !(d->tile & 0x8000);
-    if (xfuse) wsrc += dgrad_classic_bytes(d->Cout, d->Cin, d->ksize, d->stride);
-    // Darknet-53 layers 1 and 3 (3x3, 32 -> 64, stride 2 / 1): one persistent launch with the dz patch staged once and the filter in
-    // registers (conv_stem.hip); tile bit 0x8000 (the classic classes) and RYOLO_STEM_DGRAD=0 keep the implicit-GEMM launches (tests, A/B)
-    // (the stride-1 64 -> 128 layers keep the 256 x 64 tile: it carries the folded BatchNorm reduce, and the channel-split kernel measured
-    // 286 us against its 278 / 332 with the reduce -- step 48.50 vs 48.44 ms)
-    if (!g_bnred && d->ksize == 3 && d->pad == 1 && ((d->Cin == 32 && d->Cout == 64) || (d->Cin == 64 && d->Cout == 128 && d->stride == 2)) &&
-        !(d->tile & 0x80ff)) {
-        const char *e = tune(TUNE_STEM_DGRAD);
-        const int knob = e ? atoi(e) : 3;              // bit 0: the 64 -> 32 kernels, bit 1: the 128 -> 64 one (A/B; ryolo_set_tuning)
-        if (knob & (d->Cout == 64 ? 1 : 2)) {
-            const int nt_out = (long long)d->N * d->H * d->W * d->Cin * 2 >= nt_out_min_bytes() ? 1 : 0;
-            // (its size guards -- dz of 2 GiB and more, tile counts beyond 2^31 -- answer EINVAL before anything is enqueued: those launches
-            // fall through to the parity-class launches below, which served them before this kernel existed)
-            const unsigned long long dzb = (((unsigned long long)d->N * Ho * Wo - 1) * dz_cstride + d->Cout) * 2ull;
-            const unsigned long long dxb = (((unsigned long long)d->N * d->H * d->W - 1) * d->in_cstride + d->Cin) * 2ull;
-            if (dzb < 0x7fffff00ull && dxb < 0x7fffff00ull) {
-                RYOLO_CONV_DRY_RUN(RYOLO_CONV_KERNEL_STEM_DGRAD);
-                const int rc = launch_conv_stem_dgrad(d->Cout, d->stride, dz, dz_cstride, packed_dgrad, dx, d->in_cstride, accumulate, d->N, d->H,
-                                                      d->W, nt_out, cu_count(), (hipStream_t)stream_);
-                if (rc != RYOLO_EINVAL) return rc;
-            }
-        }
-    }
-    const int ncls = d->stride == 1 ? 1 : (xfuse ? 2 : 4);
-    const int wrows = xfuse ? (2 * d->Cin + 127) / 128 * 128 : rows;
-    for (int cls = 0; cls < ncls; cls++) {
-        int dy[9], dxx[9], khs[9], kws[9];
-        const int nt = xfuse ? dgrad_xfused_class(cls, dy, dxx, khs, kws, kws)
-                             : dgrad_classes(d->ksize, d->stride, d->pad, cls, dy, dxx, khs, kws);
-        ConvParams p;
-        p.x = (const __bf16 *)dz;
-        p.w = (const __bf16 *)wsrc;
-        p.scale = ones; p.shift = zeros;
-        p.res = accumulate ? (const __bf16 *)dx : nullptr;
-        p.y = (__bf16 *)dx;
-        p.N = d->N; p.H = Ho; p.W = Wo; p.Cin = d->Cout; p.in_cs = dz_cstride;
-        p.Cout = d->Cin; p.out_cs = d->in_cstride; p.res_cs = d->in_cstride;
-        p.K = nt * d->Cout;
-        p.Kpad = (p.K + BK - 1) / BK * BK;
-        p.act = RYOLO_ACT_LINEAR; p.slope = 0.f; p.ups = 1; p.nt = 0;
-        p.cin_log2 = ilog2_exact(d->Cout);
-        p.ntaps = nt;
-        if (d->stride == 1) {
-            p.stride = 1; p.pad = d->ksize - 1 - d->pad;
-            p.Ho = d->H; p.Wo = d->W;
-            for (int t = 0; t < nt; t++) { p.tap_dy[t] = dy[t]; p.tap_dx[t] = dxx[t]; }
-            p.os = 1; p.osx = 1; p.ooy = 0; p.oox = 0; p.OH = d->H; p.OW = d->W;
-        } else if (xfuse) {
-            const int a = cls;
-            p.stride = 1; p.pad = 0;
-            p.Cout = 2 * d->Cin; p.out_cs = 2 * d->in_cstride; p.res_cs = 2 * d->in_cstride;
-            p.Ho = (d->H - a + 1) / 2; p.Wo = d->W / 2;                 // rows of this parity x pixel PAIRS
-            for (int t = 0; t < nt; t++) { p.tap_dy[t] = dy[t]; p.tap_dx[t] = dxx[t]; }
-            p.os = 2; p.osx = 1; p.ooy = a; p.oox = 0; p.OH = d->H; p.OW = d->W / 2;
-            if (p.Ho <= 0 || p.Wo <= 0) { wsrc += ((size_t)wrows * p.Kpad + 128) * 2; continue; }
-        } else {
-            const int a = cls >> 1, b = cls & 1;
-            p.stride = 1; p.pad = 0;
-            p.Ho = (d->H - a + 1) / 2; p.Wo = (d->W - b + 1) / 2;      // grid of input pixels with this parity
-            for (int t = 0; t < nt; t++) { p.tap_dy[t] = dy[t]; p.tap_dx[t] = dxx[t]; }
-            p.os = 2; p.osx = 2; p.ooy = a; p.oox = b; p.OH = d->H; p.OW = d->W;
-            if (p.Ho <= 0 || p.Wo <= 0) { wsrc += ((size_t)rows * p.Kpad + 128) * 2; continue; }
-        }
-        for (int t = nt; t < 9; t++) { p.tap_dy[t] = 0; p.tap_dx[t] = 0; }
-        p.M = (int)((long long)d->N * p.Ho * p.Wo);
-        const unsigned long long xb = (((unsigned long long)d->N * Ho * Wo - 1) * dz_cstride + d->Cout) * 2ull;
-        const unsigned long long wb = ((unsigned long long)wrows * p.Kpad + 128) * 2ull;
-        p.fast = (d->Cout % BK == 0) && xb < 0x7fffff00ull && wb < 0x7fffff00ull;
-        p.taps2 = 0;
-        if (!p.fast && (d->stride != 1 || (d->ksize == 3 && p.cin_log2 < 0))) return RYOLO_EINVAL;
-        p.x_bytes = (unsigned)(p.fast ? xb : 0);
-        p.w_bytes = (unsigned)(p.fast ? wb : 0);
-        p.stat_part = nullptr; p.stat_cpad = 0;
-        p.no_persist = (d->tile & 0x200) ? 1 : 0;
-        p.force_persist = 0;
-        p.pw_grid_cap = (d->tile & 0xff) == 13 ? (d->tile >> 16) & 0xff : 0;
-        p.ntiles = 0; p.magic_wo = p.magic_ho = p.magic_nt = 0;
-        p.nt_out = (long long)d->N * d->H * d->W * d->Cin * 2 >= nt_out_min_bytes() ? 1 : 0;
-        const int pick = (d->tile & 0xff);   // 0 = auto
-        const int rc = dispatch(p, d->ksize, pick, (hipStream_t)stream_);
-        if (rc != RYOLO_OK) return rc;
-        wsrc += ((size_t)wrows * p.Kpad + 128) * 2;
-    }
-    return RYOLO_OK;
+    rc = launch_kernel<conv0_bwd_finalize_kernel>(dim3(1), dim3(32), 0, stream, part, scale, mean, invstd, 1.0f / (float)p.M, kb, kd, dgamma, dbeta,
+                                                  act == RYOLO_ACT_LEAKY ? dslope : nullptr);
+    if (rc != RYOLO_OK) return rc;
+    return launch_c8_mode(act, p, gpw, nblk, bw, 3, stream);
 }
 
 }  // extern "C"

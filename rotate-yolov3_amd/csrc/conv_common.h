@@ -1,6 +1,8 @@
-// rotate-yolov3_amd/csrc/conv_common.h -- types and device helpers shared by the convolution translation units
-// (conv.hip: 128x128 / 256x64 / 256x32 tiles, first-layer direct kernel, packers; conv_mp.hip: the 256-wide
-// multi-phase kernel).  Internal to libryolo_hip.so; the C ABI is include/ryolo.h.
+// rotate-yolov3_amd/csrc/conv_common.h -- types, device helpers and host launch helpers shared by the convolution translation units:
+// conv.hip (128x128 / 256x64 / 256x32 tiles, first-layer direct kernel, dispatch() and the forward entry points), conv_dgrad.hip (data
+// gradient: tap classes, packers, the folded BatchNorm-reduce plan), conv_mp.hip (256-wide multi-phase kernel), conv_mq.hip (two
+// workgroups per CU), conv_pw.hip (weight-stationary 1x1), conv_stem.hip (stem layers).  Internal to libryolo_hip.so; the C ABI is
+// include/ryolo.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -181,55 +183,130 @@ __device__ __forceinline__ void split_pixel(int m, int Wo, int Ho, unsigned magi
 }
 
 
-// ryolo_conv_kernel_choice() / ryolo_conv_dgrad_kernel_choice(): a dry run of the dispatch.  While this pointer is set (conv.hip),
-// every launcher of the convolution units writes the code of the kernel it is about to launch there and returns RYOLO_OK instead
-// of launching -- the decision is reported from the launch site itself, behind every size guard and fall-through, not from a
-// parallel copy of the decision tree.
-extern thread_local int *g_conv_choice;
-#define RYOLO_CONV_DRY_RUN(code)          \
-    do {                                  \
-        if (ryolo_detail::g_conv_choice) { \
-            *ryolo_detail::g_conv_choice = (code); \
-            return RYOLO_OK;              \
-        }                                 \
+// ---- host side --------------------------------------------------------------------------------------------------------------------
+// What a launch needs besides its ConvParams, passed explicitly from the entry point through dispatch() to every launcher.
+//   bnred / bnred_mode  ryolo_conv2d_dgrad_bnreduce: the launch must carry the folded BatchNorm-backward reduce, in the kernel
+//                       bnreduce_plan chose (its caller sized the partial rows for that launch): 1 conv_pw.hip's MODE 3, 2 the persistent
+//                       2x2 tile (one row per workgroup), 3 a one-tile-per-workgroup tile (one row per pixel tile), 4 conv_mq.hip's
+//                       128-channel tiles (one row per workgroup)
+//   choice              ryolo_conv_kernel_choice() / ryolo_conv_dgrad_kernel_choice(): a dry run of the dispatch.  Every launcher writes
+//                       the code of the kernel it is about to launch there and returns RYOLO_OK instead of launching -- the decision is
+//                       reported from the launch site itself, behind every size guard and fall-through, not from a parallel copy of the
+//                       decision tree
+struct ConvLaunch {
+    hipStream_t stream = nullptr;
+    const BnRed *bnred = nullptr;
+    int bnred_mode = 0;
+    int *choice = nullptr;
+};
+#define RYOLO_CONV_DRY_RUN(lc, code)  \
+    do {                              \
+        if ((lc).choice) {            \
+            *(lc).choice = (code);    \
+            return RYOLO_OK;          \
+        }                             \
     } while (0)
+
+// compute units of the current device (256 when it cannot be asked), read once
+inline int cu_count() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
+    }();
+    return cus;
+}
+
+// Launch KFN; RYOLO_OK or RYOLO_ELAUNCH.  A kernel that takes more than 64 KiB of dynamic LDS has its limit raised first, once per kernel
+// function (the static belongs to this instantiation, i.e. to KFN, and its initialisation is thread-safe).
+template <auto KFN, typename... Args>
+int launch_kernel(dim3 grid, dim3 block, size_t smem, hipStream_t stream, Args... args) {
+    if (smem > 64 * 1024) {
+        static const hipError_t raised = hipFuncSetAttribute((const void *)KFN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (raised != hipSuccess) return RYOLO_ELAUNCH;
+    }
+    hipLaunchKernelGGL(KFN, grid, block, smem, stream, args...);
+    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+}
+
+// Bytes of `npix` NHWC bf16 pixels of stride `cs` of which the last uses `c` channels, as the extent of a buffer descriptor; false when
+// the kernels' 31-bit byte offsets do not reach that far.  (A packed filter of `rows` rows: npix = rows, cs = Kpad, c = Kpad + 128.)
+inline bool buffer_extent(unsigned long long npix, long long cs, long long c, unsigned *bytes = nullptr) {
+    const unsigned long long b = ((npix - 1) * (unsigned long long)cs + (unsigned long long)c) * 2ull;
+    if (b >= 0x7fffff00ull) return false;
+    if (bytes) *bytes = (unsigned)b;
+    return true;
+}
+
+// The persistent grid of the implicit-GEMM tiles over M pixels x Cout channels in BM x BN tiles: its size (two workgroups per CU, a
+// multiple of 8 for the XCD chunking), whether the tile list is deep enough for it to win -- at least rounds2 / 2 rounds (measured at 2.5:
+// 1444 tiles 0.030 -> 0.028 ms, 722 tiles 0.021 -> 0.022), or just more than one round when forced -- and whether the kernel's
+// multiply-high divisions are exact.  The ONE statement of that rule: dispatch(), launch_variant(), the conv_mq128 picks and bnreduce_plan
+// (which sizes the partial rows for the grid launched) all ask here.
+struct PersistGrid {
+    int grid, nt;
+    long long tiles;
+    bool deep, exact;
+};
+inline PersistGrid persist_grid(long long M, int BM, int Cout, int BN, int Ho, int Wo, bool force = false, int rounds2 = 5) {
+    const long long mt = (M + BM - 1) / BM, nt = (Cout + BN - 1) / BN, dmax = Wo > Ho ? Wo : Ho;
+    PersistGrid g;
+    g.grid = (2 * cu_count()) & ~7;
+    g.nt = (int)nt;
+    g.tiles = mt * nt;
+    g.deep = force ? g.tiles > g.grid : 2 * g.tiles >= (long long)rounds2 * g.grid;
+    g.exact = g.grid >= 8 && mt * BM * dmax < 0x100000000ll && g.tiles * nt < 0x100000000ll;
+    return g;
+}
+
+inline int ilog2_exact(int v) {
+    int l = 0;
+    while ((1 << l) < v) l++;
+    return (1 << l) == v ? l : -1;
+}
+
+// conv.hip, for conv_dgrad.hip: descriptor check, the dispatch of one launch, and the switches both units read
+int conv_validate(const ryolo_conv_desc *d);
+int dispatch(ConvParams &p, int ksize, int pick, const ConvLaunch &lc);
+long long nt_out_min_bytes();
+bool conv_pw_disabled();
+int mq128_knob();
 
 // conv_mp.hip: 256-channel x BM-pixel workgroup tile, 8 waves, multi-phase K loop (FAST path only).
 // Returns RYOLO_EINVAL when the shape does not qualify (caller falls back to the other tiles).
-int launch_conv_mp(ConvParams &p, int bm /* 256, 192, 0 = pick */, int variant, hipStream_t stream);
+int launch_conv_mp(ConvParams &p, int bm /* 256, 192, 0 = pick */, int variant, const ConvLaunch &lc);
 int conv_mp_pick_bm(const ConvParams &p);
 bool conv_mp_eligible(const ConvParams &p);
 // conv_mq.hip: 128-pixel x 256-channel tile, 4 waves, two independent workgroups per CU (same eligibility as conv_mp)
-int launch_conv_mq(ConvParams &p, int variant, hipStream_t stream);
-// ... and its 128-CHANNEL members (round 5): bm = 128 or 64 pixels per tile; C_out % 128 == 0, otherwise conv_mq's conditions.  bnred
+int launch_conv_mq(ConvParams &p, int variant, const ConvLaunch &lc);
+// ... and its 128-CHANNEL members (round 5): bm = 128 or 64 pixels per tile; C_out % 128 == 0, otherwise conv_mq's conditions.  lc.bnred
 // (stride-1 launches without statistics): the folded BatchNorm reduce, one row of part[conv_mq128_grid()][3][C] per workgroup
 bool conv_mq128_eligible(const ConvParams &p);
 int conv_mq128_grid(const ConvParams &p, int bm);    // workgroups of the launch (= rows of BatchNorm-reduce partials), 0 = not served
-int launch_conv_mq128(ConvParams &p, int bm, const BnRed *bnred, hipStream_t stream);
+int launch_conv_mq128(ConvParams &p, int bm, const ConvLaunch &lc);
 // conv_stem.hip: 3x3, C_in 32 -> C_out 64, stride 1 / 2: the input patch of an 8 x 32 output block staged once, the filter in registers
 bool conv_stem_eligible(const ConvParams &p, int ksize);
-int launch_conv_stem(ConvParams &p, int cus, hipStream_t stream);
+int launch_conv_stem(ConvParams &p, const ConvLaunch &lc);
 bool conv_stem64_eligible(const ConvParams &p, int ksize);      // conv_stem.hip: 3x3 / 1, 64 -> 128
-int launch_conv_stem64(ConvParams &p, int cus, hipStream_t stream);
+int launch_conv_stem64(ConvParams &p, const ConvLaunch &lc);
 // conv_stem.hip: Darknet-53 layer 0 (3x3, 8 -> 32) forward with its input patch staged in LDS (no statistics); slope_dev: optional device
 // scalar for leaky / PReLU; round_z: BatchNorm applied to z rounded to bf16 (training recompute)
-int launch_conv0_halo(ConvParams &p, const float *slope_dev, int round_z, int cus, hipStream_t stream);
+int launch_conv0_halo(ConvParams &p, const float *slope_dev, int round_z, const ConvLaunch &lc);
 // conv_stem.hip: the data gradients of the two 3x3 32 -> 64 stem layers (64 -> 32 channels in the gradient's direction) as one persistent
 // launch each -- stride 2: all four output-parity classes from one staged dz patch, w_classes = the four classic class images of
 // ryolo_conv_pack_weights_dgrad; stride 1: its single nine-tap image
 // cdz = channels of dz: 64 (layers 1 / 3) or 128 (layer 5, stride 2 only: the waves split the output channels)
 int launch_conv_stem_dgrad(int cdz, int stride, const void *dz, int dz_cs, const void *w_classes, void *dx, int dx_cs, int accumulate, int N,
-                           int H, int W, int nt_out, int cus, hipStream_t stream);
+                           int H, int W, int nt_out, const ConvLaunch &lc);
 // ... and two stem layers in one launch (inference): the 32-channel tensor between them is computed into LDS, never stored
 int conv_stem_pair_kind(const ryolo_conv_desc *first, const ryolo_conv_desc *second, int shortcut_from_input);
 int launch_conv_stem_pair(int kind, ConvParams &p /* the second layer */, const void *x, unsigned x_bytes, int in_cs, int H, int W,
                           const void *w_first, int kpad_first, const float *scale_first, const float *shift_first, int act_first,
-                          float slope_first, int cus, hipStream_t stream);
+                          float slope_first, hipStream_t stream);
 // conv_pw.hip: 1x1 stride-1 layers (and their data gradients), weight-stationary: the filter slice in registers, rows through an LDS ring
 bool conv_pw_eligible(const ConvParams &p, int ksize);
 bool conv_pw_preferred(const ConvParams &p);        // the shapes on which it beats the 128 x 128 tile (auto dispatch)
 int conv_pw_grid(const ConvParams &p);             // workgroups (= rows of BatchNorm-reduce partials) of the launch, 0 = not served
-int launch_conv_pw(ConvParams &p, const void *bnred /* const BnRed * or nullptr */, hipStream_t stream);
+int launch_conv_pw(ConvParams &p, const ConvLaunch &lc);      // lc.bnred: the folded BatchNorm reduce (MODE 3)
 // a YOLO head (1x1, K = 256, na*no <= 512 channels) decoded from the accumulators: io / p rows out, no head tensor
 bool conv_pw_decode_supported(const ConvParams &p, int na, int no);
 int launch_conv_pw_decode(ConvParams &p, float *io, long long io_img_rows, long long io_row0, float *pout, const float *anchors, int na, int no,

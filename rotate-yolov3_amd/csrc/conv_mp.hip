@@ -608,32 +608,14 @@ __global__ void __launch_bounds__(512) conv_mp_kernel(const ConvParams p) {
 
 inline unsigned mp_magic_u32(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 
-inline int mp_cu_count() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-    }
-    return cus;
-}
-
 void *g_trace_buf = nullptr;
 int g_dbg[4] = {0, 0, 0, 0};
 int g_var[16] = {0};
 
 template <int BM, int GEN, int VAR, int KO = 0>
-int mp_launch(ConvParams &p, hipStream_t stream) {
+int mp_launch(ConvParams &p, const ConvLaunch &lc) {
     if (VAR & (128 | 1024)) p.stat_part = (double *)g_trace_buf;
-    static bool attr_done = false;
     constexpr int LDS = GEN == 1 ? MP_LDS_GEN : MP_LDS;
-    auto kfn = conv_mp_kernel<BM, GEN, VAR, KO>;
-    if (!attr_done && !g_conv_choice) {
-        if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-            return RYOLO_ELAUNCH;
-        attr_done = true;
-    }
     const int mt = (p.M + BM - 1) / BM;
     p.nt = (p.Cout + MP_BN - 1) / MP_BN;
     const long long T = (long long)mt * p.nt;
@@ -651,12 +633,11 @@ int mp_launch(ConvParams &p, hipStream_t stream) {
         p.y_bytes = (unsigned)yb;
         p.res_bytes = (unsigned)rb;
     }
-    RYOLO_CONV_DRY_RUN(BM == 192 ? RYOLO_CONV_KERNEL_MP192 : RYOLO_CONV_KERNEL_MP256);
-    int cus = mp_cu_count() & ~7;
+    RYOLO_CONV_DRY_RUN(lc, BM == 192 ? RYOLO_CONV_KERNEL_MP192 : RYOLO_CONV_KERNEL_MP256);
+    int cus = cu_count() & ~7;
     if (g_dbg[1] >= 8) cus = g_dbg[1] & ~7;   // ablation builds: cap on the persistent grid (0 in the product)
     const int grid = T >= cus ? cus : (int)((T + 7) & ~7ll);   // a multiple of 8 (XCD chunking); surplus workgroups exit at once
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(512), LDS, stream, p);
-    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+    return launch_kernel<conv_mp_kernel<BM, GEN, VAR, KO>>(dim3((unsigned)grid), dim3(512), LDS, lc.stream, p);
 }
 
 }  // namespace
@@ -670,7 +651,7 @@ bool conv_mp_eligible(const ConvParams &p) {
 
 // BM that minimises (rounds of the persistent grid) x (tile height): 256 unless 192 saves a quarter round or more
 int conv_mp_pick_bm(const ConvParams &p) {
-    const long long cus = mp_cu_count() & ~7, nt = (p.Cout + MP_BN - 1) / MP_BN;
+    const long long cus = cu_count() & ~7, nt = (p.Cout + MP_BN - 1) / MP_BN;
     long long best = 0, best_bm = 256;
     for (int bm : {256, 192}) {
         const long long tiles = ((long long)p.M + bm - 1) / bm * nt;
@@ -680,7 +661,7 @@ int conv_mp_pick_bm(const ConvParams &p) {
     return (int)best_bm;
 }
 
-int launch_conv_mp(ConvParams &p, int bm, int variant, hipStream_t stream) {
+int launch_conv_mp(ConvParams &p, int bm, int variant, const ConvLaunch &lc) {
     if (!conv_mp_eligible(p)) return RYOLO_EINVAL;
     const int gen = p.stat_part != nullptr ? 1 : (p.os != 1 ? 2 : 0);
     if (bm == 0) bm = conv_mp_pick_bm(p);
@@ -689,7 +670,7 @@ int launch_conv_mp(ConvParams &p, int bm, int variant, hipStream_t stream) {
     // schedule variants and timing-only ablations (several of them produce WRONG results): never in the shipped library
     if (gen == 0 && variant != 0) {
         p.dbg0 = g_dbg[0];
-#define MP_VAR(V) case V: return bm == 256 ? mp_launch<256, 0, V>(p, stream) : mp_launch<192, 0, V>(p, stream);
+#define MP_VAR(V) case V: return bm == 256 ? mp_launch<256, 0, V>(p, lc) : mp_launch<192, 0, V>(p, lc);
         switch (variant) {
             MP_VAR(1) MP_VAR(2) MP_VAR(8) MP_VAR(16) MP_VAR(32) MP_VAR(40) MP_VAR(64) MP_VAR(512) MP_VAR(144) MP_VAR(1024) MP_VAR(1056) MP_VAR(1032)
             default: return RYOLO_EINVAL;
@@ -707,13 +688,13 @@ int launch_conv_mp(ConvParams &p, int bm, int variant, hipStream_t stream) {
         if (m && !e) cm = p.ntaps > 1 && p.Cin >= atoi(m);
     }
     if (bm == 256) {
-        if (gen == 1) return cm ? mp_launch<256, 1, 0, 1>(p, stream) : mp_launch<256, 1, 0>(p, stream);
-        if (gen == 2) return cm ? mp_launch<256, 2, 0, 1>(p, stream) : mp_launch<256, 2, 0>(p, stream);
-        return cm ? mp_launch<256, 0, 0, 1>(p, stream) : mp_launch<256, 0, 0>(p, stream);
+        if (gen == 1) return cm ? mp_launch<256, 1, 0, 1>(p, lc) : mp_launch<256, 1, 0>(p, lc);
+        if (gen == 2) return cm ? mp_launch<256, 2, 0, 1>(p, lc) : mp_launch<256, 2, 0>(p, lc);
+        return cm ? mp_launch<256, 0, 0, 1>(p, lc) : mp_launch<256, 0, 0>(p, lc);
     }
-    if (gen == 1) return cm ? mp_launch<192, 1, 0, 1>(p, stream) : mp_launch<192, 1, 0>(p, stream);
-    if (gen == 2) return cm ? mp_launch<192, 2, 0, 1>(p, stream) : mp_launch<192, 2, 0>(p, stream);
-    return cm ? mp_launch<192, 0, 0, 1>(p, stream) : mp_launch<192, 0, 0>(p, stream);
+    if (gen == 1) return cm ? mp_launch<192, 1, 0, 1>(p, lc) : mp_launch<192, 1, 0>(p, lc);
+    if (gen == 2) return cm ? mp_launch<192, 2, 0, 1>(p, lc) : mp_launch<192, 2, 0>(p, lc);
+    return cm ? mp_launch<192, 0, 0, 1>(p, lc) : mp_launch<192, 0, 0>(p, lc);
 }
 
 }  // namespace ryolo_detail

@@ -684,17 +684,6 @@ __global__ void __launch_bounds__(256, 2) conv_mq_kernel(const ConvParams p, con
 
 inline unsigned mq_magic_u32(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 
-inline int mq_cu_count() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-    }
-    return cus;
-}
-
 #ifdef RYOLO_MP_ABLATION
 void *g_q_trace_buf = nullptr;
 int g_q_dbg[4] = {0, 0, 0, 0};
@@ -710,25 +699,18 @@ inline int mq_grid_for(long long T, int cw = 64) {
         const int v = e ? atoi(e) : 2;
         if (v >= 1 && v <= 4) per_cu = v;
     }
-    const int wgs = per_cu * (mq_cu_count() & ~7);
+    const int wgs = per_cu * (cu_count() & ~7);
     return T >= wgs ? wgs : (int)((T + 7) & ~7ll);
 }
 
 template <int GEN, int VAR, int CW = 64, int PF = 8, bool BNRED = false, int FS = 1, int KO = 0>
-int mq_launch(ConvParams &p, const BnRed *bnred, hipStream_t stream) {
+int mq_launch(ConvParams &p, const ConvLaunch &lc) {
     using L = QL<CW, PF>;
 #ifdef RYOLO_MP_ABLATION
     if (VAR & 1024) p.stat_part = (double *)g_q_trace_buf;
     p.dbg0 = g_q_dbg[0];
 #endif
-    static bool attr_done = false;
     constexpr int LDS = GEN == 1 ? L::LDS_GEN : (BNRED ? L::LDS_RED : L::LDS);
-    auto kfn = conv_mq_kernel<GEN, VAR, CW, PF, BNRED, FS, KO>;
-    if (!attr_done && !g_conv_choice) {
-        if (hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-            return RYOLO_ELAUNCH;
-        attr_done = true;
-    }
     const int mt = (p.M + L::BM - 1) / L::BM;
     p.nt = (p.Cout + L::BN - 1) / L::BN;
     const long long T = (long long)mt * p.nt;
@@ -748,8 +730,8 @@ int mq_launch(ConvParams &p, const BnRed *bnred, hipStream_t stream) {
     }
     BnRed br = BnRed();
     if constexpr (BNRED) {
-        if (!bnred || p.nt > L::STAT_NT || (p.Cout % L::BN) != 0) return RYOLO_EINVAL;
-        br = *bnred;
+        if (!lc.bnred || p.nt > L::STAT_NT || (p.Cout % L::BN) != 0) return RYOLO_EINVAL;
+        br = *lc.bnred;
         const unsigned long long zb = (((unsigned long long)p.M - 1) * br.z_cs + p.Cout) * 2ull;
         if (zb >= 0x7fffff00ull) return RYOLO_EINVAL;
         br.z_bytes = (unsigned)zb;
@@ -760,7 +742,7 @@ int mq_launch(ConvParams &p, const BnRed *bnred, hipStream_t stream) {
         p.reg3 = reg ? 1 : 0;
     }
     p.korder = KO;
-    RYOLO_CONV_DRY_RUN((CW == 64 ? RYOLO_CONV_KERNEL_MQ : (PF == 8 ? RYOLO_CONV_KERNEL_MQ128 : RYOLO_CONV_KERNEL_MQ64)));
+    RYOLO_CONV_DRY_RUN(lc, (CW == 64 ? RYOLO_CONV_KERNEL_MQ : (PF == 8 ? RYOLO_CONV_KERNEL_MQ128 : RYOLO_CONV_KERNEL_MQ64)));
     int grid = mq_grid_for(T, CW);
 #ifdef RYOLO_MP_ABLATION
     if (g_q_dbg[1] >= 8) {
@@ -768,20 +750,19 @@ int mq_launch(ConvParams &p, const BnRed *bnred, hipStream_t stream) {
         grid = T >= wgs ? wgs : (int)((T + 7) & ~7ll);
     }
 #endif
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(256), LDS, stream, p, br);
-    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+    return launch_kernel<conv_mq_kernel<GEN, VAR, CW, PF, BNRED, FS, KO>>(dim3((unsigned)grid), dim3(256), LDS, lc.stream, p, br);
 }
 
 }  // namespace
 
 namespace ryolo_detail {
 
-int launch_conv_mq(ConvParams &p, int variant, hipStream_t stream) {
+int launch_conv_mq(ConvParams &p, int variant, const ConvLaunch &lc) {
     if (!conv_mp_eligible(p)) return RYOLO_EINVAL;
     const int gen = p.stat_part != nullptr ? 1 : (p.os != 1 ? 2 : 0);
 #ifdef RYOLO_MP_ABLATION
     if (gen == 0 && variant != 0) {
-#define MQ_VAR(V) case V: return mq_launch<0, V>(p, nullptr, stream);
+#define MQ_VAR(V) case V: return mq_launch<0, V>(p, lc);
         switch (variant) {
             MQ_VAR(8) MQ_VAR(16) MQ_VAR(32) MQ_VAR(40) MQ_VAR(48) MQ_VAR(1024) MQ_VAR(1056) MQ_VAR(1032) MQ_VAR(2) MQ_VAR(4) MQ_VAR(1026) MQ_VAR(1028) MQ_VAR(18) MQ_VAR(20) MQ_VAR(256) MQ_VAR(272)
             default: return RYOLO_EINVAL;
@@ -805,8 +786,8 @@ int launch_conv_mq(ConvParams &p, int variant, hipStream_t stream) {
     if (gen == 1) {     // statistics epilogue: the two-block order too (its row sums are flushed per block: twice as often) -- bs-64 step 50.05 vs
                         // 50.20 ms (A/B on one box, profiles/r05_ab_log.txt); RYOLO_MQ_SWEEP_STATS = 1 restores one sweep per half
         const char *es = abl_env("RYOLO_MQ_SWEEP_STATS");
-        if (es && atoi(es) == 1) return mq_launch<1, 0>(p, nullptr, stream);
-        return cm ? mq_launch<1, 0, 64, 8, false, 2, 1>(p, nullptr, stream) : mq_launch<1, 0, 64, 8, false, 2>(p, nullptr, stream);
+        if (es && atoi(es) == 1) return mq_launch<1, 0>(p, lc);
+        return cm ? mq_launch<1, 0, 64, 8, false, 2, 1>(p, lc) : mq_launch<1, 0, 64, 8, false, 2>(p, lc);
     }
     // The epilogue's store order (see the epilogue): two blocks of pixel groups for launches that WRITE a tensor (forward, first-writer data
     // gradients) -- HBM writes of 3x3 128->256 @76^2 at bs 32 fall from 130 to 95 MB (= the output), 1.51 -> 1.26 x the algorithmic bytes
@@ -820,11 +801,11 @@ int launch_conv_mq(ConvParams &p, int variant, hipStream_t stream) {
     // (stride-2 parity classes: the same K-order rule as conv_mp.hip's launcher, so the two kernels add in the same order on every launch
     //  either of them can serve -- ADVICE r5: conv_mp took the channel-major order here and conv_mq did not)
     if (gen == 2) {
-        if (two) return cm ? mq_launch<2, 0, 64, 8, false, 2, 1>(p, nullptr, stream) : mq_launch<2, 0, 64, 8, false, 2>(p, nullptr, stream);
-        return cm ? mq_launch<2, 0, 64, 8, false, 1, 1>(p, nullptr, stream) : mq_launch<2, 0>(p, nullptr, stream);
+        if (two) return cm ? mq_launch<2, 0, 64, 8, false, 2, 1>(p, lc) : mq_launch<2, 0, 64, 8, false, 2>(p, lc);
+        return cm ? mq_launch<2, 0, 64, 8, false, 1, 1>(p, lc) : mq_launch<2, 0>(p, lc);
     }
-    if (two) return cm ? mq_launch<0, 0, 64, 8, false, 2, 1>(p, nullptr, stream) : mq_launch<0, 0, 64, 8, false, 2>(p, nullptr, stream);
-    return cm ? mq_launch<0, 0, 64, 8, false, 1, 1>(p, nullptr, stream) : mq_launch<0, 0>(p, nullptr, stream);
+    if (two) return cm ? mq_launch<0, 0, 64, 8, false, 2, 1>(p, lc) : mq_launch<0, 0, 64, 8, false, 2>(p, lc);
+    return cm ? mq_launch<0, 0, 64, 8, false, 1, 1>(p, lc) : mq_launch<0, 0>(p, lc);
 }
 
 // ---- the 128-channel members of the family (CW = 32): 128-pixel and 64-pixel tiles
@@ -841,25 +822,25 @@ int conv_mq128_grid(const ConvParams &p, int bm) {
 // The 128-channel members are instantiated in the MEASUREMENT BUILD only (round 6): built, correct, no faster than the tiles they would
 // replace (profiles/r05_mq128_bench.txt), so the shipped library neither dispatches nor contains them; tools/mq128_bench.py runs on the
 // ablation library.
-int launch_conv_mq128(ConvParams &p, int bm, const BnRed *bnred, hipStream_t stream) {
+int launch_conv_mq128(ConvParams &p, int bm, const ConvLaunch &lc) {
 #ifndef RYOLO_MP_ABLATION
-    (void)p; (void)bm; (void)bnred; (void)stream;
+    (void)p; (void)bm; (void)lc;
     return RYOLO_EINVAL;
 #else
     if (!conv_mq128_eligible(p) || (bm != 128 && bm != 64)) return RYOLO_EINVAL;
     const int gen = p.stat_part != nullptr ? 1 : (p.os != 1 ? 2 : 0);
-    if (bnred) {
+    if (lc.bnred) {
         if (gen != 0) return RYOLO_EINVAL;
-        return bm == 128 ? mq_launch<0, 0, 32, 8, true>(p, bnred, stream) : mq_launch<0, 0, 32, 4, true>(p, bnred, stream);
+        return bm == 128 ? mq_launch<0, 0, 32, 8, true>(p, lc) : mq_launch<0, 0, 32, 4, true>(p, lc);
     }
     if (bm == 128) {
-        if (gen == 1) return mq_launch<1, 0, 32, 8>(p, nullptr, stream);
-        if (gen == 2) return mq_launch<2, 0, 32, 8>(p, nullptr, stream);
-        return mq_launch<0, 0, 32, 8>(p, nullptr, stream);
+        if (gen == 1) return mq_launch<1, 0, 32, 8>(p, lc);
+        if (gen == 2) return mq_launch<2, 0, 32, 8>(p, lc);
+        return mq_launch<0, 0, 32, 8>(p, lc);
     }
-    if (gen == 1) return mq_launch<1, 0, 32, 4>(p, nullptr, stream);
-    if (gen == 2) return mq_launch<2, 0, 32, 4>(p, nullptr, stream);
-    return mq_launch<0, 0, 32, 4>(p, nullptr, stream);
+    if (gen == 1) return mq_launch<1, 0, 32, 4>(p, lc);
+    if (gen == 2) return mq_launch<2, 0, 32, 4>(p, lc);
+    return mq_launch<0, 0, 32, 4>(p, lc);
 #endif
 }
 

@@ -544,16 +544,8 @@ static thread_local const PwDecode *g_pw_decode = nullptr;      // set around th
 template <int KT, int NW, int CF, int PF, int RING, int MODE>
 int pw_launch(ConvParams &p, const PwBnRed &br, int grid, hipStream_t stream) {
     constexpr int LDS = RING * PF * 16 * 128 + (MODE == 4 ? PF * 16 * (NW * CF * 16 * 2 + 16) : 0);
-    static bool attr_done = false;
-    auto kfn = conv_pw_kernel<KT, NW, CF, PF, RING, MODE>;
-    if (!attr_done) {
-        if (LDS > 64 * 1024 && hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-            return RYOLO_ELAUNCH;
-        attr_done = true;
-    }
     const PwDecode dc = g_pw_decode ? *g_pw_decode : PwDecode{};
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(NW * 64), LDS, stream, p, br, dc);
-    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+    return launch_kernel<conv_pw_kernel<KT, NW, CF, PF, RING, MODE>>(dim3((unsigned)grid), dim3(NW * 64), LDS, stream, p, br, dc);
 }
 
 // MODES: bit m set = MODE m is instantiated for this configuration (each instantiation is ~200 registers of unrolled code)
@@ -571,22 +563,11 @@ int pw_launch_mode(ConvParams &p, const PwBnRed *br, int grid, hipStream_t strea
 
 inline unsigned pw_magic_u32(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 
-inline int pw_cu_count() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-    }
-    return cus;
-}
-
 // which configuration serves (K, C_out, M); returns false when none does.  NB = channel blocks, wgpc = workgroups per CU.
 bool pw_pick(const ConvParams &p, bool bnred, PwCfg &c, int &NB, int &grid) {
     if (p.Kpad != p.Cin || (p.Cin & 63)) return false;
     const int kt = p.Cin / 64;
-    const int cus = pw_cu_count() & ~7;
+    const int cus = cu_count() & ~7;
     if (cus < 8) return false;
     int wgpc;
     // a YOLO head decoded from the accumulators: all (<= 512) channels in one workgroup, 8 waves x 64
@@ -674,7 +655,9 @@ int launch_conv_pw_decode(ConvParams &p, float *io, long long io_img_rows, long 
     dc.na = na; dc.no = no; dc.ny = p.Ho; dc.nx = p.Wo; dc.stride = stride; dc.cf = cf; dc.arc = arc;
     dc.apb = pw_decode_apb(na, no, p.Cin == 1024 ? 128 : 256);
     g_pw_decode = &dc;
-    const int rc = launch_conv_pw(p, nullptr, stream);
+    ConvLaunch lc;
+    lc.stream = stream;
+    const int rc = launch_conv_pw(p, lc);
     g_pw_decode = nullptr;
     return rc;
 }
@@ -705,14 +688,14 @@ static int g_pw_dbg = 0;
 static unsigned *g_pw_trace = nullptr;
 #endif
 
-int launch_conv_pw(ConvParams &p, const void *bnred /* conv.hip BnRed or nullptr */, hipStream_t stream) {
+int launch_conv_pw(ConvParams &p, const ConvLaunch &lc) {
 #ifdef RYOLO_MP_ABLATION
     p.dbg0 = g_pw_dbg;
     p.trace = g_pw_trace;
 #endif
     PwCfg c;
     int NB, grid;
-    if (!pw_pick(p, bnred != nullptr, c, NB, grid)) return RYOLO_EINVAL;
+    if (!pw_pick(p, lc.bnred != nullptr, c, NB, grid)) return RYOLO_EINVAL;
     const int bms = c.pf * 16;
     const long long mb = ((long long)p.M + bms - 1) / bms;
     const unsigned long long yb = (((unsigned long long)p.M * p.ups * p.ups - 1) * p.out_cs + p.Cout) * 2ull;
@@ -729,9 +712,8 @@ int launch_conv_pw(ConvParams &p, const void *bnred /* conv.hip BnRed or nullptr
     p.magic_ho = pw_magic_u32(p.Ho);
     PwBnRed br{};
     const PwBnRed *brp = nullptr;
-    if (bnred) {
+    if (const BnRed *b = lc.bnred) {
         if (p.stat_part || p.ups != 1) return RYOLO_EINVAL;
-        const BnRed *b = (const BnRed *)bnred;
         br.z = b->z; br.z_cs = b->z_cs; br.scale = b->scale; br.shift = b->shift; br.mean = b->mean; br.invstd = b->invstd;
         br.slope = b->slope; br.part = b->part;
         const unsigned long long zb = (((unsigned long long)p.M - 1) * b->z_cs + p.Cout) * 2ull;
@@ -739,10 +721,10 @@ int launch_conv_pw(ConvParams &p, const void *bnred /* conv.hip BnRed or nullptr
         br.z_bytes = (unsigned)zb;
         brp = &br;
     }
-    RYOLO_CONV_DRY_RUN(RYOLO_CONV_KERNEL_PW);       // (a mode without an instantiation returns EINVAL below: the forward modes all exist)
+    RYOLO_CONV_DRY_RUN(lc, RYOLO_CONV_KERNEL_PW);       // (a mode without an instantiation returns EINVAL below: the forward modes all exist)
 #define PW_CASE(KT_, NW_, CF_, PF_, RING_, MODES_)                                               \
     if (c.kt == KT_ && c.nw == NW_ && c.cf == CF_ && c.pf == PF_ && c.ring == RING_)              \
-        return pw_launch_mode<KT_, NW_, CF_, PF_, RING_, MODES_>(p, brp, grid, stream);
+        return pw_launch_mode<KT_, NW_, CF_, PF_, RING_, MODES_>(p, brp, grid, lc.stream);
     PW_CASE(4, 4, 2, 8, 4, 3)      // (no accumulate-operand instantiation: it needs 12 spilled registers inside the loop; such launches take the 128x128 tile)
     PW_CASE(6, 4, 2, 4, 8, 7)
     PW_CASE(2, 8, 2, 4, 12, 15)

@@ -346,13 +346,9 @@ __global__ void __launch_bounds__(256) conv0_halo_kernel(const ConvParams p, con
 static int launch_conv0_halo_t(ConvParams &p, const float *slope_dev, int round_z, int act, int grid, int tiles_x, int tiles_y, int ntiles,
                                hipStream_t stream) {
     constexpr int smem = 2 * C0_BUF;
-    if (act == RYOLO_ACT_LEAKY)
-        hipLaunchKernelGGL(conv0_halo_kernel<RYOLO_ACT_LEAKY>, dim3((unsigned)grid), dim3(256), smem, stream, p, slope_dev, round_z, tiles_x, tiles_y, ntiles);
-    else if (act == RYOLO_ACT_MISH)
-        hipLaunchKernelGGL(conv0_halo_kernel<RYOLO_ACT_MISH>, dim3((unsigned)grid), dim3(256), smem, stream, p, slope_dev, round_z, tiles_x, tiles_y, ntiles);
-    else
-        hipLaunchKernelGGL(conv0_halo_kernel<RYOLO_ACT_LINEAR>, dim3((unsigned)grid), dim3(256), smem, stream, p, slope_dev, round_z, tiles_x, tiles_y, ntiles);
-    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+    if (act == RYOLO_ACT_LEAKY) return launch_kernel<conv0_halo_kernel<RYOLO_ACT_LEAKY>>(dim3((unsigned)grid), dim3(256), smem, stream, p, slope_dev, round_z, tiles_x, tiles_y, ntiles);
+    if (act == RYOLO_ACT_MISH) return launch_kernel<conv0_halo_kernel<RYOLO_ACT_MISH>>(dim3((unsigned)grid), dim3(256), smem, stream, p, slope_dev, round_z, tiles_x, tiles_y, ntiles);
+    return launch_kernel<conv0_halo_kernel<RYOLO_ACT_LINEAR>>(dim3((unsigned)grid), dim3(256), smem, stream, p, slope_dev, round_z, tiles_x, tiles_y, ntiles);
 }
 
 // ------------------------------------------------------------------------------------------------ data gradients of layers 1 and 3
@@ -937,22 +933,12 @@ __global__ void __launch_bounds__(256, 2) conv3x3_c64_halo_kernel(const ConvPara
 
 template <bool STATS, int ACT>
 int launch_stem64(ConvParams &p, int grid, int tiles_x, int tiles_y, int ntiles, hipStream_t stream) {
-    hipLaunchKernelGGL((conv3x3_c64_halo_kernel<STATS, ACT>), dim3((unsigned)grid), dim3(256), c64::BYTES, stream, p, tiles_x, tiles_y, ntiles);
-    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+    return launch_kernel<conv3x3_c64_halo_kernel<STATS, ACT>>(dim3((unsigned)grid), dim3(256), c64::BYTES, stream, p, tiles_x, tiles_y, ntiles);
 }
 
 template <int S, bool STATS>
 int launch_stem(ConvParams &p, int grid, int tiles_x, int tiles_y, int ntiles, hipStream_t stream) {
-    constexpr int smem = Patch<S>::BYTES;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (smem > 64 * 1024 && hipFuncSetAttribute((const void *)conv3x3_c32_halo_kernel<S, STATS>,
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-            return RYOLO_ELAUNCH;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((conv3x3_c32_halo_kernel<S, STATS>), dim3((unsigned)grid), dim3(256), smem, stream, p, tiles_x, tiles_y, ntiles);
-    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+    return launch_kernel<conv3x3_c32_halo_kernel<S, STATS>>(dim3((unsigned)grid), dim3(256), Patch<S>::BYTES, stream, p, tiles_x, tiles_y, ntiles);
 }
 
 }  // namespace
@@ -969,17 +955,17 @@ bool conv_stem64_eligible(const ConvParams &p, int ksize) {
            !(p.stat_part && p.res) && (long long)p.N * p.H * p.W * p.in_cs * 2 < 0x7fffff00ll;
 }
 
-int launch_conv_stem64(ConvParams &p, int cus, hipStream_t stream) {
+int launch_conv_stem64(ConvParams &p, const ConvLaunch &lc) {
     const int tiles_x = (p.Wo + c64::TWX - 1) / c64::TWX, tiles_y = (p.Ho + c64::TH - 1) / c64::TH;
     const long long nt = (long long)p.N * tiles_x * tiles_y;
     if (nt > 0x7fffffffll) return RYOLO_EINVAL;
-    RYOLO_CONV_DRY_RUN(RYOLO_CONV_KERNEL_STEM64);
-    int grid = (2 * cus) & ~7;
+    RYOLO_CONV_DRY_RUN(lc, RYOLO_CONV_KERNEL_STEM64);
+    int grid = (2 * cu_count()) & ~7;
     if (grid < 8) grid = 8;
-    if (p.stat_part) return launch_stem64<true, RYOLO_ACT_LINEAR>(p, grid, tiles_x, tiles_y, (int)nt, stream);
-    if (p.act == RYOLO_ACT_LEAKY) return launch_stem64<false, RYOLO_ACT_LEAKY>(p, grid, tiles_x, tiles_y, (int)nt, stream);
-    if (p.act == RYOLO_ACT_MISH) return launch_stem64<false, RYOLO_ACT_MISH>(p, grid, tiles_x, tiles_y, (int)nt, stream);
-    return launch_stem64<false, RYOLO_ACT_LINEAR>(p, grid, tiles_x, tiles_y, (int)nt, stream);
+    if (p.stat_part) return launch_stem64<true, RYOLO_ACT_LINEAR>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream);
+    if (p.act == RYOLO_ACT_LEAKY) return launch_stem64<false, RYOLO_ACT_LEAKY>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream);
+    if (p.act == RYOLO_ACT_MISH) return launch_stem64<false, RYOLO_ACT_MISH>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream);
+    return launch_stem64<false, RYOLO_ACT_LINEAR>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream);
 }
 
 // The stride-2 data gradient one level down (Darknet-53 layer 5: 3x3 / 2, 64 -> 128; 128 -> 64 channels in the gradient's direction).  The filter (9 x 128 x 64 bf16 = 147 KB) only fits the registers of a workgroup if the WAVES SPLIT THE OUTPUT
@@ -1102,7 +1088,7 @@ __global__ void __launch_bounds__(256, 2) dgrad3x3_s2_c128_kernel(const DgS2Para
 }
 
 int launch_conv_stem_dgrad(int cdz, int stride, const void *dz, int dz_cs, const void *w_classes, void *dx, int dx_cs, int accumulate, int N,
-                           int H, int W, int nt_out, int cus, hipStream_t stream) {
+                           int H, int W, int nt_out, const ConvLaunch &lc) {
     const int Ho = stride == 2 ? (H - 1) / 2 + 1 : H, Wo = stride == 2 ? (W - 1) / 2 + 1 : W;
     const unsigned long long dzb = (((unsigned long long)N * Ho * Wo - 1) * dz_cs + cdz) * 2ull;
     if ((stride != 1 && stride != 2) || (cdz != 64 && !(cdz == 128 && stride == 2)) || dzb >= 0x7fffff00ull || (dz_cs & 7) || (dx_cs & 7) || dz_cs < cdz ||
@@ -1118,59 +1104,48 @@ int launch_conv_stem_dgrad(int cdz, int stride, const void *dz, int dz_cs, const
     const long long nt = (long long)q.tiles_x * q.tiles_y * N;
     if (nt >= 0x7fffffff) return RYOLO_EINVAL;
     q.ntiles = (int)nt; q.nt_out = nt_out;
-    int grid = (2 * cus) & ~7;
+    int grid = (2 * cu_count()) & ~7;
     if (grid < 8) grid = 8;
-    if (cdz == 64) {
-        if (stride == 2) hipLaunchKernelGGL(dgrad3x3_c64_kernel<2>, dim3((unsigned)grid), dim3(256), 2 * DgTile<2>::BUF, stream, q);
-        else hipLaunchKernelGGL(dgrad3x3_c64_kernel<1>, dim3((unsigned)grid), dim3(256), 2 * DgTile<1>::BUF, stream, q);
-    } else {
-        hipLaunchKernelGGL(dgrad3x3_s2_c128_kernel, dim3((unsigned)grid), dim3(256), 2 * DgTile128::BUF, stream, q);
-    }
-    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+    const dim3 g((unsigned)grid), b(256);
+    if (cdz == 128) return launch_kernel<dgrad3x3_s2_c128_kernel>(g, b, 2 * DgTile128::BUF, lc.stream, q);
+    if (stride == 2) return launch_kernel<dgrad3x3_c64_kernel<2>>(g, b, 2 * DgTile<2>::BUF, lc.stream, q);
+    return launch_kernel<dgrad3x3_c64_kernel<1>>(g, b, 2 * DgTile<1>::BUF, lc.stream, q);
 }
 
 // p: x (8-channel NHWC, x_bytes), w, scale, shift, y, out_cs, H = Ho, W = Wo, N, Kpad, act, slope, nt_out; no statistics (those passes keep
 // the direct kernel: conv.hip)
-int launch_conv0_halo(ConvParams &p, const float *slope_dev, int round_z, int cus, hipStream_t stream) {
+int launch_conv0_halo(ConvParams &p, const float *slope_dev, int round_z, const ConvLaunch &lc) {
     if (!p.y || p.stat_part) return RYOLO_EINVAL;
     const int tiles_x = (p.Wo + C0_TW - 1) / C0_TW, tiles_y = (p.Ho + C0_TH - 1) / C0_TH;
     const long long nt = (long long)p.N * tiles_x * tiles_y;
     if (nt > 0x7fffffffll) return RYOLO_EINVAL;
-    int grid = (4 * cus) & ~7;
+    int grid = (4 * cu_count()) & ~7;
     if (grid < 8) grid = 8;
-    return launch_conv0_halo_t(p, slope_dev, round_z, p.act, grid, tiles_x, tiles_y, (int)nt, stream);
+    return launch_conv0_halo_t(p, slope_dev, round_z, p.act, grid, tiles_x, tiles_y, (int)nt, lc.stream);
 }
 
-int launch_conv_stem(ConvParams &p, int cus, hipStream_t stream) {
+int launch_conv_stem(ConvParams &p, const ConvLaunch &lc) {
     const int th = p.stride == 1 ? Patch<1>::TH : Patch<2>::TH;
     const int tiles_x = (p.Wo + TW - 1) / TW, tiles_y = (p.Ho + th - 1) / th;
     const long long nt = (long long)p.N * tiles_x * tiles_y;
     if (nt > 0x7fffffffll) return RYOLO_EINVAL;
-    RYOLO_CONV_DRY_RUN(RYOLO_CONV_KERNEL_STEM);
-    int grid = (2 * cus) & ~7;
+    RYOLO_CONV_DRY_RUN(lc, RYOLO_CONV_KERNEL_STEM);
+    int grid = (2 * cu_count()) & ~7;
     if (grid < 8) grid = 8;
-    if (p.stat_part) return p.stride == 1 ? launch_stem<1, true>(p, grid, tiles_x, tiles_y, (int)nt, stream)
-                                          : launch_stem<2, true>(p, grid, tiles_x, tiles_y, (int)nt, stream);
-    return p.stride == 1 ? launch_stem<1, false>(p, grid, tiles_x, tiles_y, (int)nt, stream)
-                         : launch_stem<2, false>(p, grid, tiles_x, tiles_y, (int)nt, stream);
+    if (p.stat_part) return p.stride == 1 ? launch_stem<1, true>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream)
+                                          : launch_stem<2, true>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream);
+    return p.stride == 1 ? launch_stem<1, false>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream)
+                         : launch_stem<2, false>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream);
 }
 
-static int launch_pair(ConvParams &p, const PairFirst &f, int cus, hipStream_t stream) {
+static int launch_pair(ConvParams &p, const PairFirst &f, hipStream_t stream) {
     using G = PairGeom;
     const int tiles_x = (p.Wo + TW - 1) / TW, tiles_y = (p.Ho + G::P::TH - 1) / G::P::TH;
     const long long nt = (long long)p.N * tiles_x * tiles_y;
     if (nt > 0x7fffffffll) return RYOLO_EINVAL;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (G::BYTES > 64 * 1024 && hipFuncSetAttribute((const void *)conv_stem_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                        G::BYTES) != hipSuccess)
-            return RYOLO_ELAUNCH;
-        attr_done = true;
-    }
-    int grid = (2 * cus) & ~7;
+    int grid = (2 * cu_count()) & ~7;
     if (grid < 8) grid = 8;
-    hipLaunchKernelGGL(conv_stem_pair_kernel, dim3((unsigned)grid), dim3(256), G::BYTES, stream, p, f, tiles_x, tiles_y, (int)nt);
-    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+    return launch_kernel<conv_stem_pair_kernel>(dim3((unsigned)grid), dim3(256), G::BYTES, stream, p, f, tiles_x, tiles_y, (int)nt);
 }
 
 // kind of pair (first, second) the fused launch serves: 2 = (1x1, 64 -> 32) -> (3x3/1 pad 1, 32 -> 64) with the shortcut from the first
@@ -1185,12 +1160,12 @@ int conv_stem_pair_kind(const ryolo_conv_desc *a, const ryolo_conv_desc *b, int 
 }
 
 int launch_conv_stem_pair(int kind, ConvParams &p, const void *x, unsigned x_bytes, int in_cs, int H, int W, const void *w_first, int kpad_first,
-                          const float *scale_first, const float *shift_first, int act_first, float slope_first, int cus, hipStream_t stream) {
+                          const float *scale_first, const float *shift_first, int act_first, float slope_first, hipStream_t stream) {
     PairFirst f;
     f.x = (const __bf16 *)x; f.w = (const __bf16 *)w_first; f.scale = scale_first; f.shift = shift_first; f.x_bytes = x_bytes;
     f.in_cs = in_cs; f.Kpad = kpad_first; f.act = act_first; f.slope = slope_first; f.H = H; f.W = W;
     (void)kind;
-    return launch_pair(p, f, cus, stream);
+    return launch_pair(p, f, stream);
 }
 
 }  // namespace ryolo_detail

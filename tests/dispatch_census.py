@@ -157,12 +157,12 @@ def _gemm_bits(code, M, Cout, ks, cus, stats, res, os_, force, kpad):
         bm = 128 if code == 9 else 64
         T = -(-M // bm) * -(-Cout // 128)
         return (M % bm != 0, Cout % 128 != 0) + _grid_bits(T, 2 * (cus & ~7))
-    if code >= 16:              # conv.hip:1301 igemm_tile_code; 1415-1433 launch_variant's persistent grid
+    if code >= 16:              # conv.hip igemm_tile_code(); launch_variant()'s persistent grid (conv_common.h persist_grid())
         bm, bn, waves, nst = {1: (128, 128, 8, 2), 2: (256, 64, 4, 2), 3: (256, 32, 4, 2), 4: (256, 128, 8, 3), 6: (128, 128, 8, 2),
                               7: (128, 128, 4, 2)}[code - 16]
         T = -(-M // bm) * -(-Cout // bn)
         grid = (2 * cus) & ~7
-        # conv.hip:1671-1678: the 1x1 128 x 128 auto pick leaves the persistent layout to the 4-wave tile; conv.hip:1655-1659 force_persist
+        # conv.hip dispatch(): the 1x1 128 x 128 auto pick leaves the persistent layout to the 4-wave tile; its short-K 3x3 rule sets force_persist
         no_persist = code == 17 and ks == 1
         persist_ok = os_ == 1 and (not stats or (waves == 4 and not res))
         persistent = False
@@ -258,7 +258,7 @@ def edge_bits(rec, cus):
     if form in ("eval", "train"):
         stats = form == "train" and rec["stats"]
         res = form == "eval" and rec["residual"]
-        if code == 4:            # conv.hip:1765-1773: 16-pixel groups, 32 groups per wave, 4 waves per block
+        if code == 4:            # conv.hip conv0_params(): 16-pixel groups, 32 groups per wave, 4 waves per block
             M = N * Ho * Wo
             return dict(part_group=M % 16 != 0, part_block=M % (16 * 32 * 4) != 0)
         if code == 8:            # conv_stem.hip:232 (8 x 64 tiles), 1136-1140 grid 4 x CUs
@@ -272,14 +272,14 @@ def edge_bits(rec, cus):
         if code == 6:
             return dict(zip(names4, _pw_bits(M, Cout, Cin, cus)))
         kpad = -(-(k * k * Cin) // BK) * BK
-        force = k == 3 and kpad // BK <= 9 and not (stats and (res or code == 18))    # conv.hip:1655-1659
+        force = k == 3 and kpad // BK <= 9 and not (stats and (res or code == 18))    # conv.hip dispatch(): the short-K 3x3 rule
         bits = _gemm_bits(code, M, Cout, k, cus, stats, res, 1, force, kpad)
         return dict(zip(names4, bits), part_cstride=out_cs != Cout, idle_wgs=_idle_wgs(code, M, Cout, cus))
     if form == "dgrad":
         if code == 7:            # conv_stem.hip:1115-1122 (8 x 64 stride 2 / 4 x 32 stride 1 / 8 x 32 the 128-channel kernel)
             th, tw = (8, 64) if (Cin == 32 and s == 2) else ((4, 32) if Cin == 32 else (8, 32))
             return dict(zip(("part_right", "part_bottom", "underfull", "ragged"), _spatial_bits(H, W, N, th, tw, (2 * cus) & ~7)))
-        # conv.hip:2481-2546: stride 1 is one launch over the input pixels; stride 2 is two x-fused classes (pixel pairs, 2 C_in channels)
+        # conv_dgrad.hip conv_dgrad(): stride 1 is one launch over the input pixels; stride 2 is two x-fused classes (pixel pairs, 2 C_in channels)
         # or four parity classes, each a launch with its own pixel count
         launches = []
         if s == 1:

@@ -63,3 +63,51 @@ def test_census_examples_of_the_issue():
     L = dc._L()
     d = dc.mk_desc(heads[0]["desc"])
     assert L.ryolo_conv_wgrad_kernel_choice(C.byref(d)) == 128
+
+
+def test_dry_run_queries_answer_the_same_from_two_threads():
+    """The dry-run queries carry their launch context as an argument, so no state survives a call: two threads asking the forward-with-
+    statistics, data-gradient, data-gradient-with-reduce and reduce-rows questions of the bs-64 training blocks at once, in opposite
+    order, get the serial answers.  The blocks reach every reduce plan of the shipped library: conv_pw.hip (mode 1), the persistent 2x2
+    tile (mode 2) and the one-tile-per-workgroup tiles (mode 3)."""
+    import threading
+    L = dc._L()
+    recs = dc.train_blocks(dc.config_defs("darknet53", 1, 608, 608), 608, 608, 64)
+    descs = {r["desc"]: r["stats"] for r in recs if r["form"] == "train"}
+    queries = []
+    for t, stats in descs.items():
+        queries += [("fwd", t, 1 if stats else 0), ("dgrad", t, 0), ("dgrad", t, 1), ("rows", t, 0)]
+    assert len(queries) >= 48
+
+    def ask(q):
+        what, t, flag = q
+        d = dc.mk_desc(t)
+        if what == "fwd":
+            return L.ryolo_conv_kernel_choice(C.byref(d), 0, flag)
+        if what == "dgrad":
+            return L.ryolo_conv_dgrad_kernel_choice(C.byref(d), flag)
+        return L.ryolo_conv2d_dgrad_bnreduce_rows(C.byref(d))
+
+    serial = [ask(q) for q in queries]
+    fused = set(a for q, a in zip(queries, serial) if q[0] == "dgrad" and q[2] == 1)
+    # include/ryolo.h: RYOLO_CONV_KERNEL_PW = 6, RYOLO_CONV_KERNEL_IGEMM = 16 + tile code (7: the 2x2 tile, 1 / 2: 128 x 128 / 256 x 64)
+    assert 6 in fused and 16 + 7 in fused and (16 + 1 in fused or 16 + 2 in fused), fused       # modes 1, 2, 3
+    assert any(a > 0 for q, a in zip(queries, serial) if q[0] == "rows")
+
+    PASSES = 50
+    got = {}
+    start = threading.Barrier(2)
+
+    def worker(name, order):
+        start.wait()
+        got[name] = [[ask(queries[i]) for i in order] for _ in range(PASSES)]
+
+    n = len(queries)
+    threads = [threading.Thread(target=worker, args=("up", list(range(n)))),
+               threading.Thread(target=worker, args=("down", list(range(n - 1, -1, -1))))]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    assert got["up"] == [serial] * PASSES
+    assert got["down"] == [serial[::-1]] * PASSES

@@ -33,7 +33,7 @@ extern "C" {
 
 const char *ryolo_strerror(int code);
 /* ABI version; bumped when a signature or a contract changes.  3: ryolo_rnms_workspace_bytes grew (the split scan's state words) and
- * ryolo_set_tuning was added since 2; ryolo_rnms on a capturing stream runs unsplit. */
+ * ryolo_set_tuning was added since 2; ryolo_rnms on a capturing stream runs unsplit.  4: ryolo_se_workspace_bytes / ryolo_se_nhwc added. */
 int ryolo_abi_version(void);
 /* "RYOLO_BUILD_ID=" + 16 hex digits: a hash of the library's sources, headers and compiler flags (__graft_entry__.source_id()). */
 const char *ryolo_build_id(void);
@@ -244,6 +244,26 @@ int ryolo_upsample_nhwc(const void *x, int x_cstride, void *y, int y_cstride, in
                         void *stream); /* scale 1 = slice copy */
 int ryolo_maxpool_nhwc(const void *x, int x_cstride, void *y, int y_cstride, int N, int H, int W, int C, int ksize,
                        int stride, void *stream);
+
+/* Squeeze-and-excitation block (inference) -- replaces SELayer.forward (model/models.py:27-31):
+ *   m[n,c] = mean over H,W of x[n,c,:,:];  g[n,:] = sigmoid(W2 . relu(W1 . m[n,:]));  y[n,c,h,w] = x[n,c,h,w] * g[n,c].
+ *   x, y        NHWC bf16 [N, H, W, C]; either may be a channel slice of a wider buffer: `*_cstride` = elements between pixels,
+ *               >= C and a multiple of 8, base address 16-byte aligned.  y must not overlap x (the block's input has a second reader,
+ *               the residual skip): two disjoint channel slices of one buffer are fine.
+ *   w1          fp32 [hidden][C]  = fc.0.weight (nn.Linear(C, C/16, bias=False), models.py:21);
+ *   w2          fp32 [C][hidden]  = fc.2.weight (nn.Linear(C/16, C, bias=False), models.py:23).
+ *   gate_out    fp32 [N][C] (may be NULL): receives g.
+ *   workspace   ryolo_se_workspace_bytes(N, H, W, C) bytes of device scratch, 16-byte aligned (contents irrelevant on entry).
+ * Arithmetic: the mean, both products and the sigmoid 1 / (1 + expf(-t)) are fp32 on the bf16 values of x; y is rounded to bf16 once.
+ * The pixel sum is split into chunks that depend on (H, W, C) alone and is combined in a fixed order without atomics: results are
+ * bit-identical from run to run and do not depend on the batch size.  Three launches on `stream` (pool partial sums, gate, scale).
+ * Served: C % 8 == 0, 16 <= C <= 2048, 1 <= hidden <= 128, N <= 65535.  RYOLO_EINVAL: a null pointer (other than gate_out), a size
+ * outside these, a misaligned pointer or stride, workspace_bytes below the reported size, y overlapping x.  The workspace query
+ * returns 0 for a shape that is not served. */
+size_t ryolo_se_workspace_bytes(int N, int H, int W, int C);
+int ryolo_se_nhwc(const void *x, int x_cstride, const float *w1 /* fp32 [hidden][C] */, const float *w2 /* fp32 [C][hidden] */,
+                  int hidden, void *y, int y_cstride, int N, int H, int W, int C,
+                  float *gate_out /* fp32 [N][C], may be NULL */, void *workspace, size_t workspace_bytes, void *stream);
 
 
 /* ------------------------------------------------------------------------------------------------

@@ -44,6 +44,9 @@ _sigs = {
     "ryolo_conv_head_decode_supported": (C.c_int, [_dp, C.c_int, C.c_int]),
     "ryolo_conv0_recompute_supported": (C.c_int, [_dp]),
     "ryolo_conv2d_dgrad_bnreduce_rows": (C.c_int, [_dp]),
+    # squeeze-and-excitation (csrc/se.hip)
+    "ryolo_se_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ryolo_se_nhwc": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp]),
 }
 
 

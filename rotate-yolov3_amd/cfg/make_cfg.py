@@ -6,6 +6,8 @@ topologies are produced by code so that width/height/anchors/classes are paramet
 
   darknet53(...)   Darknet-53 trunk + 3-scale FPN head, 75 convs / 23 shortcuts / 4 routes / 2 upsamples / 3 yolo
                    (layer indices as SURVEY.md Appendix A: yolo at 82, 94, 106; routes 83, 86, 95, 98)
+  darknet53_se(...)  the same with a squeeze-and-excitation block in front of every residual unit of the 256 / 512 / 1024
+                   stages (the reference's cfg/ICDAR/yolov3_608_se.cfg and cfg/HRSC+/yolov3_512_se.cfg): 127 layers, 20 se
   tiny(...)        yolov3-tiny: 13 convs, 6 maxpools, 2 yolo heads
 
     python -m rotate_yolov3_amd.cfg.make_cfg darknet53 > yolov3.cfg
@@ -33,7 +35,9 @@ def _yolo(mask, anchors, classes):
     return ["[yolo]", "mask = %s" % mask, "anchors = %s" % anchors, "classes=%d" % classes, "num=9", ""]
 
 
-def darknet53(width=608, height=608, anchors="ara " + ANCHORS_ARA, classes=1, na_per_head=72, masks=None):
+def darknet53(width=608, height=608, anchors="ara " + ANCHORS_ARA, classes=1, na_per_head=72, masks=None, se=False):
+    """se=True: [se] + conv 1x1 + conv 3x3 + shortcut from=-4 in the 256 / 512 / 1024 stages (the skip comes from in front of the se);
+    the absolute route indices 61 and 36 stay as they are and then name shortcut layers inside the 38^2 and 76^2 stages"""
     no = na_per_head * (classes + 6)
     masks = masks or ["%d-%d" % (2 * na_per_head, 3 * na_per_head - 1), "%d-%d" % (na_per_head, 2 * na_per_head - 1),
                       "0-%d" % (na_per_head - 1)]
@@ -42,7 +46,10 @@ def darknet53(width=608, height=608, anchors="ara " + ANCHORS_ARA, classes=1, na
     for filters, nblocks in ((64, 1), (128, 2), (256, 8), (512, 8), (1024, 4)):
         L += _conv(filters, 3, 2)
         for _ in range(nblocks):
-            L += _conv(filters // 2, 1, 1) + _conv(filters, 3, 1) + ["[shortcut]", "from=-3", "activation=linear", ""]
+            if se and filters >= 256:
+                L += ["[se]", "channels=%d" % filters, ""]
+            L += _conv(filters // 2, 1, 1) + _conv(filters, 3, 1)
+            L += ["[shortcut]", "from=%d" % (-4 if se and filters >= 256 else -3), "activation=linear", ""]
     # head 0 @ stride 32
     for _ in range(3):
         L += _conv(512, 1, 1) + _conv(1024, 3, 1)
@@ -60,6 +67,11 @@ def darknet53(width=608, height=608, anchors="ara " + ANCHORS_ARA, classes=1, na
         L += _conv(128, 1, 1) + _conv(256, 3, 1)
     L += _conv(no, 1, 1, bn=0, act="linear") + _yolo(masks[2], anchors, classes)
     return "\n".join(L) + "\n"
+
+
+def darknet53_se(width=608, height=608, anchors="ara " + ANCHORS_ARA, classes=1, na_per_head=72, masks=None):
+    """the topology of the reference's cfg/ICDAR/yolov3_608_se.cfg: se blocks at layers 13, 17, ..., 41, 46, ..., 74, 79, ..., 91"""
+    return darknet53(width, height, anchors, classes, na_per_head, masks, se=True)
 
 
 def tiny(width=608, height=608, anchors=TINY_PAIRS, classes=80):
@@ -80,4 +92,4 @@ def tiny(width=608, height=608, anchors=TINY_PAIRS, classes=80):
 
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "darknet53"
-    sys.stdout.write({"darknet53": darknet53, "tiny": tiny}[which]())
+    sys.stdout.write({"darknet53": darknet53, "darknet53_se": darknet53_se, "tiny": tiny}[which]())

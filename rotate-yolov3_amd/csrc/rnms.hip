@@ -976,7 +976,8 @@ const char *ryolo_strerror(int code) {
     }
 }
 
-int ryolo_abi_version(void) { return 3; }      // 3: the NMS workspace sizes grew and ryolo_set_tuning was added since 2; a capturing stream runs ryolo_rnms unsplit
+int ryolo_abi_version(void) { return 4; }      // 3: the NMS workspace sizes grew and ryolo_set_tuning was added since 2; a capturing stream runs ryolo_rnms unsplit
+                                                // 4: ryolo_se_workspace_bytes / ryolo_se_nhwc (csrc/se.hip)
 
 void ryolo_rnms_count_pairs(uint64_t *device_counter) { g_pair_counter = (unsigned long long *)device_counter; }
 

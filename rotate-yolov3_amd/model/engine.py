@@ -13,6 +13,7 @@ per launch.  The plan:
   * BatchNorm (eval) is folded to fp32 scale/shift applied on the fp32 accumulator (utils/torch_utils.py:45-69),
     PReLU(1)/LeakyReLU become the epilogue's slope;
   * the three YOLO decodes write straight into one [bs, sum(na*ny*nx), no] tensor (the torch.cat of models.py:298).
+  * `se` layers run ryolo_se_nhwc (csrc/se.hip: pool, gate, scale) into a buffer of their own: their input has a second reader.
 Whatever cannot be folded falls back to the small NHWC kernels of csrc/yolo.hip (add / upsample / copy / maxpool).
 All launches go to torch's current stream through the C ABI; after a warm-up the sequence can be replayed from a
 hipGraph (`use_graph=True`).
@@ -111,6 +112,10 @@ class HipEngine(object):
         def flops(i, hw):
             return 2.0 * params[i]['k'] ** 2 * params[i]['cin'] * params[i]['cout'] * hw[1] * hw[2] * self.bs
 
+        # one scratch for every se layer: the ops are serial on one stream
+        se_bytes = max([_lib.lib().ryolo_se_workspace_bytes(self.bs, op['out'].H, op['out'].W, op['C']) for op in pl.ops if op['kind'] == 'se'] or [0])
+        se_ws = torch.empty(se_bytes, dtype=torch.uint8, device=device) if se_bytes else None
+
         for op in pl.ops:
             kind, i = op['kind'], op['layer']
             xin, out = tv(op.get('xin')), tv(op.get('out'))
@@ -156,6 +161,13 @@ class HipEngine(object):
             elif kind == 'add':
                 self.ops.append(self._mk_add(tv(op['a']), tv(op['b']), out))
                 info.update(bytes=6.0 * out.numel())
+            elif kind == 'se':
+                # fp32 copies taken now: a later in-place edit of the parameters rebuilds the engine (Darknet._drop_stale_eval_engines)
+                w1 = mods[i].fc[0].weight.detach().to(device=device, dtype=torch.float32).contiguous().clone()
+                w2 = mods[i].fc[2].weight.detach().to(device=device, dtype=torch.float32).contiguous().clone()
+                self.keep += [w1, w2, se_ws]
+                self.ops.append(self._mk_se(xin, w1, w2, out, se_ws))
+                info.update(bytes=3.0 * 2.0 * out.numel())
             elif kind == 'maxpool':
                 self.ops.append(self._mk_maxpool(xin, out, op['size'], op['stride']))
                 info.update(bytes=2.0 * (xin.numel() + out.numel()))
@@ -253,6 +265,11 @@ class HipEngine(object):
         def run():
             _lib.check(_lib.lib().ryolo_add_nhwc(a.data_ptr(), a.stride(2), b.data_ptr(), b.stride(2), out.data_ptr(),
                                                  out.stride(2), n * h * w, c, _lib.stream_ptr(self.device)), "ryolo_add_nhwc")
+        return run
+
+    def _mk_se(self, xin, w1, w2, out, ws):
+        def run():
+            ops.se_nhwc(xin, w1, w2, out=out, workspace=ws)
         return run
 
     def _mk_upsample(self, xin, out, s):

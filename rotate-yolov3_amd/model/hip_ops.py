@@ -87,6 +87,39 @@ def conv2d_bn_act(x, packed_w, scale, shift, cout, ksize, stride=1, pad=None, ac
     return out
 
 
+def se_workspace(n, h, w, c, device):
+    """scratch of one ryolo_se_nhwc call (partial pixel sums + gates)"""
+    nbytes = _lib.lib().ryolo_se_workspace_bytes(n, h, w, c)
+    if nbytes == 0:
+        raise RuntimeError("se: unsupported shape N %d, H %d, W %d, C %d (C must be a multiple of 8 from 16 to 2048)" % (n, h, w, c))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def se_nhwc(x, w1, w2, out=None, gate_out=None, workspace=None):
+    """y = x * sigmoid(W2 . relu(W1 . mean_hw(x))) -- SELayer.forward on NHWC bf16 (possibly slices); w1 [hidden, C] and w2 [C, hidden]
+    fp32 contiguous (fc.0.weight / fc.2.weight); gate_out: fp32 [N, C] that receives the gates."""
+    x_cs = _check_nhwc(x, "x")
+    n, h, w, c = x.shape
+    hidden = w1.shape[0]
+    for t, shape, name in ((w1, (hidden, c), "w1"), (w2, (c, hidden), "w2")):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise RuntimeError("%s must be a contiguous fp32 GPU tensor of shape %s" % (name, shape))
+    if out is None:
+        out = torch.empty((n, h, w, c), dtype=torch.bfloat16, device=x.device)
+    y_cs = _check_nhwc(out, "out")
+    assert tuple(out.shape) == (n, h, w, c), (tuple(out.shape), (n, h, w, c))
+    if gate_out is not None:
+        assert gate_out.is_cuda and gate_out.dtype == torch.float32 and gate_out.is_contiguous() and tuple(gate_out.shape) == (n, c)
+    if workspace is None:
+        workspace = se_workspace(n, h, w, c, x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().ryolo_se_nhwc(x.data_ptr(), x_cs, w1.data_ptr(), w2.data_ptr(), hidden, out.data_ptr(), y_cs, n, h, w, c,
+                                      gate_out.data_ptr() if gate_out is not None else None, workspace.data_ptr(), workspace.numel(),
+                                      _lib.stream_ptr(x.device))
+    _lib.check(rc, "ryolo_se_nhwc")
+    return out
+
+
 def pair_descs(x, first, second, out_cs=None):
     """ConvDesc pair for conv2d_bn_act_pair; first / second = dicts(cout, ksize, stride, pad, act, slope)"""
     in_cs = _check_nhwc(x, "x")

@@ -36,6 +36,23 @@ class Mish(nn.Module):
         return x * torch.tanh(F.softplus(x))
 
 
+class SELayer(nn.Module):
+    """Squeeze-and-excitation block (models.py:16-31): same attributes, so the state_dict keys are `fc.0.weight` / `fc.2.weight`.
+    On the GPU in eval mode HipEngine runs it as ryolo_se_nhwc (csrc/se.hip); this forward is the ATen chain."""
+
+    def __init__(self, channel, reduction=16):
+        super(SELayer, self).__init__()
+        self.avg_pool = nn.AdaptiveAvgPool2d(1)
+        self.fc = nn.Sequential(nn.Linear(channel, channel // reduction, bias=False), nn.ReLU(inplace=True),
+                                nn.Linear(channel // reduction, channel, bias=False), nn.Sigmoid())
+
+    def forward(self, x):
+        b, c, _, _ = x.size()
+        y = self.avg_pool(x).view(b, c)
+        y = self.fc(y).view(b, c, 1, 1)
+        return x * y.expand_as(x)
+
+
 def create_modules(module_defs, arc, hyp):
     """cfg dicts -> nn.ModuleList + routes (models.py:36-164).  `module_defs` loses its [net] block, as in the
     reference; the popped block is returned third."""
@@ -82,6 +99,9 @@ def create_modules(module_defs, arc, hyp):
             else:
                 modules = maxpool
             filters = output_filters[-1]
+        elif t == 'se':
+            modules = SELayer(int(mdef['channels']))     # models.py:89-91; `filters` carries over from the previous layer
+            filters = output_filters[-1]
         elif t == 'upsample':
             modules = nn.Upsample(scale_factor=int(mdef['stride']), mode='nearest')
             filters = output_filters[-1]
@@ -114,7 +134,7 @@ def create_modules(module_defs, arc, hyp):
                     print('WARNING: smart bias initialization failure.')
             filters = output_filters[-1]
         else:
-            raise ValueError('Unsupported layer type in cfg: %r (se / d-convolutional / weight_from are out of scope, '
+            raise ValueError('Unsupported layer type in cfg: %r (d-convolutional / weight_from are out of scope, '
                              'SURVEY.md section 2)' % t)
         module_list.append(modules)
         output_filters.append(filters)
@@ -208,7 +228,7 @@ class Darknet(nn.Module):
         output = []
         for i, (mdef, module) in enumerate(zip(self.module_defs, self.module_list)):
             mtype = mdef['type']
-            if mtype in ['convolutional', 'upsample', 'maxpool']:
+            if mtype in ['convolutional', 'upsample', 'maxpool', 'se']:
                 x = module(x)
             elif mtype == 'route':
                 layers = [int(v) for v in mdef['layers'].split(',')]

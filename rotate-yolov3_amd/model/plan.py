@@ -135,7 +135,7 @@ def plan_eval(defs, convs, yolos, N, H, W, stem_pair=True, head_decode=True, cin
       pair      layer (the second conv), first, xin, out, shortcut, descs, name
       head      layer (the yolo layer), conv, xin, desc, na, no, name
       add       layer, a, b, out            upsample  layer, xin, out, stride        maxpool   layer, xin, out, size, stride
-      copy      layer (the route), xin, out  decode    layer, xin
+      copy      layer (the route), xin, out  decode    layer, xin                     se        layer, xin, out, C
     descriptors are tuples in ConvDesc field order."""
     n = len(defs)
     shp = _shapes(defs, convs, cin, H, W)
@@ -166,7 +166,7 @@ def plan_eval(defs, convs, yolos, N, H, W, stem_pair=True, head_decode=True, cin
     for i, srcs in concat.items():
         views[i] = _new(buffers, *shp[i])
         for src, off in srcs:
-            if src not in home and defs[src]['type'] in ('convolutional', 'shortcut', 'upsample', 'maxpool') and src < i \
+            if src not in home and defs[src]['type'] in ('convolutional', 'shortcut', 'upsample', 'maxpool', 'se') and src < i \
                     and shp[src][0] % 8 == 0 and off % 8 == 0:
                 home[src] = _slice(views[i], off, shp[src][0])
             else:
@@ -236,6 +236,13 @@ def plan_eval(defs, convs, yolos, N, H, W, stem_pair=True, head_decode=True, cin
         elif t == 'maxpool':
             views[i] = view_for(i)
             ops.append(dict(kind='maxpool', layer=i, xin=views[i - 1], out=views[i], size=int(d['size']), stride=int(d['stride'])))
+        elif t == 'se':
+            # squeeze-and-excitation (ryolo_se_nhwc): never in place -- the residual unit behind it takes its skip from the se's input
+            c = shp[i][0]
+            if c % 8 or c < 16 or c > 2048:
+                raise Refused("se %d: %d channels (the HIP path serves multiples of 8 from 16 to 2048)" % (i, c))
+            views[i] = view_for(i)
+            ops.append(dict(kind='se', layer=i, xin=views[i - 1], out=views[i], C=c))
         elif t == 'route':
             if i in alias:
                 views[i] = views[alias[i]]
@@ -268,6 +275,9 @@ def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, 
     for i, d in enumerate(defs):
         if d['type'] == 'upsample' and int(d['stride']) != 2:
             raise Refused("training path: only x2 upsampling")
+        if d['type'] == 'se':
+            # the planner below passes over block types it has no rule for: an se cfg would train a different network
+            raise Refused("training path: se layers have no HIP training kernels (use model.backend = 'torch')")
         if d['type'] == 'maxpool':
             raise Refused("training path: maxpool graphs (yolov3-tiny) cannot train in the reference either "
                           "(model/loss.py:248 hard-codes three heads)")

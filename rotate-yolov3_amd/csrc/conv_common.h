@@ -1,4 +1,5 @@
-// rotate-yolov3_amd/csrc/conv_common.h -- types, device helpers and host launch helpers shared by the convolution translation units:
+// rotate-yolov3_amd/csrc/conv_common.h -- types, device helpers and host launch helpers shared by the convolution translation units
+// (and, for the types and launch helpers, by the training units wgrad.hip and train.hip):
 // conv.hip (128x128 / 256x64 / 256x32 tiles, first-layer direct kernel, dispatch() and the forward entry points), conv_dgrad.hip (data
 // gradient: tap classes, packers, the folded BatchNorm-reduce plan), conv_mp.hip (256-wide multi-phase kernel), conv_mq.hip (two
 // workgroups per CU), conv_pw.hip (weight-stationary 1x1), conv_stem.hip (stem layers).  Internal to libryolo_hip.so; the C ABI is
@@ -256,6 +257,12 @@ inline PersistGrid persist_grid(long long M, int BM, int Cout, int BN, int Ho, i
     g.deep = force ? g.tiles > g.grid : 2 * g.tiles >= (long long)rounds2 * g.grid;
     g.exact = g.grid >= 8 && mt * BM * dmax < 0x100000000ll && g.tiles * nt < 0x100000000ll;
     return g;
+}
+
+// blocks of `tb` threads for `total` work items, at least one and at most `cap` (the elementwise passes and the split-K reduces)
+inline int grid_for(long long total, int tb = 256, int cap = 32768) {
+    long long nb = (total + tb - 1) / tb;
+    return (int)(nb < 1 ? 1 : (nb > cap ? cap : nb));
 }
 
 inline int ilog2_exact(int v) {

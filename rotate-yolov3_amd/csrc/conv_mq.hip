@@ -36,7 +36,7 @@
 // deep).  Per K tile a wave then stages CW/16 weight pieces in two halves and PF/4 activation pieces per half, and the counted
 // waits follow: phase 0 leaves the PF/4 pieces of XA(t+2) in flight, phase 3 the CW/16 pieces of WB(t+1).  The 128-channel
 // tile holds 48 KiB of operands (2 x 16 + 16), its accumulators 64 registers -- which leaves room for the FOLDED BATCHNORM
-// REDUCE (BNRED, stride-1 data gradients that store the final gradient of a BatchNorm block's output: conv.hip bnreduce_plan
+// REDUCE (BNRED, stride-1 data gradients that store the final gradient of a BatchNorm block's output: conv_dgrad.hip bnreduce_plan
 // mode 4): the epilogue reads the block's z next to the running gradient, forms g = dy * act'(z * scale + shift) on the values
 // it stores and adds the 16-lane row sums of g, g * (z - mean), dy * min(u, 0) to wave-private LDS accumulators per channel
 // tile; every workgroup stores (not adds) its row of part[grid][3][C] at the end, in fixed order.

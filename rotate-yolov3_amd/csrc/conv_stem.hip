@@ -368,7 +368,7 @@ static int launch_conv0_halo_t(ConvParams &p, const float *slope_dev, int round_
 // agree to fp32 summation order (tests/test_train_ops_gpu.py::test_stem_stride2_dgrad_*).
 struct DgS2Params {
     const __bf16 *dz; unsigned dz_bytes; int dz_cs;
-    const __bf16 *w;                 // the four classic class images, consecutive (conv.hip: dgrad_classic_bytes)
+    const __bf16 *w;                 // the four classic class images, consecutive (conv_dgrad.hip: dgrad_classic_bytes)
     __bf16 *dx; int dx_cs;
     const __bf16 *res;               // dx itself when the gradient accumulates, else nullptr
     int H, W, Ho, Wo;                // dx (= the forward input) and dz (= the forward output) extents

@@ -1,4 +1,4 @@
-"""Python handles on the training-step entry points of the C ABI (include/ryolo.h, csrc/train.hip + csrc/conv.hip).
+"""Python handles on the training-step entry points of the C ABI (include/ryolo.h; csrc/train.hip, csrc/wgrad.hip, csrc/conv_dgrad.hip + csrc/conv.hip).
 Plumbing only: torch owns the device memory and the stream."""
 import ctypes as C
 
@@ -86,7 +86,7 @@ _lib.declare("ryolo_conv_wgrad_reduce_batch", C.c_int, [_vp, C.c_int, C.c_int, _
 
 
 class WgradReduceBatch(object):
-    """The split-K reduces of several layers as one launch (csrc/train.hip: wgrad_reduce_batch_kernel).  Every layer keeps its partial
+    """The split-K reduces of several layers as one launch (csrc/wgrad.hip: wgrad_reduce_batch_kernel).  Every layer keeps its partial
     tiles in its OWN workspace (conv_wgrad_partials); add() describes a layer's reduce, finalize() uploads the job table, run() reduces all
     of them -- bit-identical to the per-layer reduces."""
 

@@ -33,7 +33,7 @@ SIZES = SQUARE + RECT
 BATCHES = (1, 2, 4, 8, 16, 32, 64)
 
 BK = 64          # conv_common.h:21 K elements per step
-KP = 64          # train.hip:76 pixels per weight-gradient K step
+KP = 64          # wgrad.hip KP: pixels per weight-gradient K step
 WGRAD_TAPS = 1000
 
 DESC_FIELDS = [f for f, _ in ops.ConvDesc._fields_]
@@ -98,6 +98,11 @@ def eval_blocks(defs, H, W, N):
     return recs
 
 
+def _has_wgrad(b):
+    """every block but the one whose whole backward is one pass (layer 0: ryolo_conv0_bn_bwd_wgrad)"""
+    return not (b["bn"] and b["recompute"] and b["one_pass"])
+
+
 def train_blocks(defs, H, W, N):
     """TrainEngine's plan + the folded BatchNorm reduce: per conv block its descriptor and the four call forms"""
     tp = plan.plan_train(defs, _convs(defs), N, H, W)
@@ -116,7 +121,7 @@ def train_blocks(defs, H, W, N):
             code = L.ryolo_conv_dgrad_kernel_choice(C.byref(d), 1 if red else 0)
             recs.append(dict(form="dgrad", layer=b["layer"], desc=dt, code=code, bnred=red,
                              name=ops.kernel_name_of(code, dt[5], 1, dt[4])))
-        if not (b["bn"] and b["recompute"] and b["one_pass"]):
+        if _has_wgrad(b):
             code = L.ryolo_conv_wgrad_kernel_choice(C.byref(d))
             recs.append(dict(form="wgrad", layer=b["layer"], desc=dt, code=code, cin_real=3 if b["layer"] == 0 else dt[3], splits=wgrad_splits(dt, code)))
     return recs
@@ -208,7 +213,7 @@ def _spatial_bits(Ho, Wo, N, th, tw, grid):
 
 
 def wgrad_reduce_kind(S, Cout, cin_real, ks):
-    """train.hip wgrad_reduce_kind: the split-K reduce a layer takes -- 0 one element per thread, 1 four split quarters per workgroup
+    """wgrad.hip wgrad_plan (reduce_kind): the split-K reduce a layer takes -- 0 one element per thread, 1 four split quarters per workgroup
     (S >= 8), 2 the transposing 3x3 kernel (few splits, >= 2^20 weights)"""
     total = Cout * cin_real * ks * ks
     if S < 8 and ks == 3 and cin_real % 64 == 0 and total >= (1 << 20):
@@ -223,6 +228,50 @@ def wgrad_splits(t, code):
     per = (Cout * kpad * 4) if code > WGRAD_TAPS else (-(-Cout // 128) * 128 * kpad * 4)
     assert ws % per == 0, (t, ws, per)
     return ws // per
+
+
+# ------------------------------------------------------------------------------------------------ the weight gradient's host decisions
+WGRAD_TILE_VARIANTS = (0x1000, 0x2000, 0x2000 | 0x4000, 3 << 16)     # never the per-tap kernels; the square tile; the transposed tile; three splits
+WGRAD_JOB_FIELDS = ("S", "Cout", "Cin_real", "Cin_k", "ks", "Kpad", "Cout_pad", "kind", "wide", "block_end")
+_DUMMY = 4096            # a 16-byte aligned, non-null address: ryolo_conv_wgrad_reduce_job_fill stores it, nothing dereferences it
+
+
+def wgrad_plan_record(t, cin_real):
+    """(kernel code, workspace bytes, the job fields ryolo_conv_wgrad_reduce_job_fill writes) of one weight gradient"""
+    L, d, job = _L(), mk_desc(t), tr.WgradReduceJob()
+    L.ryolo_conv_wgrad_reduce_job_fill(C.byref(job), C.byref(d), cin_real, _DUMMY, _DUMMY, 0)
+    return (L.ryolo_conv_wgrad_kernel_choice(C.byref(d)), L.ryolo_conv_wgrad_workspace_bytes(C.byref(d))) + tuple(getattr(job, f) for f in WGRAD_JOB_FIELDS)
+
+
+def wgrad_plan_groups(configs=CONFIGS, sizes=SIZES, batches=BATCHES):
+    """{"config/classes/HxW": sorted [descriptor..., cin_real, record...] rows}: every distinct weight gradient of the training engine over
+    the census's input space, and the bs-64 608^2 ones again under each of WGRAD_TILE_VARIANTS"""
+    ti = DESC_FIELDS.index("tile")
+    groups = {}
+    for kind, nc in configs:
+        if kind != "darknet53":          # (the training engine's model)
+            continue
+        for (H, W) in sizes:
+            defs = config_defs(kind, nc, H, W)
+            keys = set()
+            for N in batches:
+                for b in plan.plan_train(defs, _convs(defs), N, H, W).blocks:
+                    if not _has_wgrad(b):
+                        continue
+                    t, c = tuple(b["desc"]), 3 if b["layer"] == 0 else b["desc"][3]
+                    keys.add((t, c))
+                    if (H, W, N) == (608, 608, 64):
+                        keys.update((t[:ti] + (v,) + t[ti + 1:], c) for v in WGRAD_TILE_VARIANTS)
+            groups["%s/%d/%dx%d" % (kind, nc, H, W)] = sorted(list(t) + [c] + list(wgrad_plan_record(t, c)) for t, c in keys)
+    return groups
+
+
+def wgrad_plan_hashes(groups=None):
+    """one sha256 per group of wgrad_plan_groups(): tests/golden/wgrad_plan.json holds the parent library's"""
+    import hashlib
+    import json
+    groups = wgrad_plan_groups() if groups is None else groups
+    return {k: hashlib.sha256(json.dumps(rows).encode()).hexdigest() for k, rows in groups.items()}
 
 
 def edge_bits(rec, cus):
@@ -245,12 +294,12 @@ def edge_bits(rec, cus):
         M = N * Ho * Wo
         S = rec["splits"]
         if code > WGRAD_TAPS:
-            # train.hip:1438-1453: K steps are 64-pixel row segments, `per` steps per split
+            # wgrad.hip wgrad_plan, the per-tap branch: K steps are 64-pixel row segments, `per` steps per split
             nsteps = N * Ho * -(-Wo // KP)
             per = -(-nsteps // S)
             return dict(ragged_split=nsteps % per != 0, part_row=Wo % KP != 0, short_row=Wo < KP, multi_split=S > 1,
                         reduce=wgrad_reduce_kind(S, Cout, rec["cin_real"], k))
-        # train.hip:1454-1564: chunk = ceil(M / S) rounded up to KP pixels; T the c_out tile (256 wide / 258-260 three-stage / square)
+        # wgrad.hip wgrad_plan, the general branch: chunk = ceil(M / S) rounded up to KP pixels; T the c_out tile (256 wide / 258-260 three-stage / square)
         chunk = -(-(-(-M // S)) // KP) * KP if S > 0 else M
         tco = 256 if code == 256 else (128 if code in (257, 258, 259) else (64 if code == 260 else code))
         return dict(ragged_split=M % chunk != 0, short_row=Wo < KP, part_k=M % KP != 0, part_co=Cout % tco != 0, multi_split=S > 1,

@@ -111,3 +111,63 @@ def test_dry_run_queries_answer_the_same_from_two_threads():
         th.join()
     assert got["up"] == [serial] * PASSES
     assert got["down"] == [serial[::-1]] * PASSES
+
+
+def test_wgrad_host_decisions_match_the_golden():
+    """Kernel code, workspace bytes and reduce job of every weight gradient of the census's input space (and of the bs-64 608^2 blocks
+    under the tile bits 0x1000 / 0x2000 / 0x6000 / a forced split count) are the ones the library gave before its host code was rewritten
+    around one plan: tests/golden/wgrad_plan.json holds one hash per (config, classes, H, W) group, generated from the parent commit's
+    library by tests/golden/gen_wgrad_plan_golden.py."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wgrad_plan.json")) as fh:
+        want = json.load(fh)["groups"]
+    got = dc.wgrad_plan_hashes()
+    assert sorted(got) == sorted(want)
+    assert len(want) == 3 * len(dc.SIZES)
+    differ = [k for k in sorted(want) if got[k] != want[k]]
+    assert not differ, "weight-gradient host decisions changed in %s" % differ
+
+
+def test_wgrad_queries_answer_the_same_from_two_threads():
+    """The weight gradient's queries compute one plan per call and keep nothing between calls: two threads asking the kernel choice, the
+    workspace size and the reduce job of the bs-64 training blocks at once, in opposite order, get the serial answers."""
+    import threading
+    L = dc._L()
+    recs = dc.train_blocks(dc.config_defs("darknet53", 1, 608, 608), 608, 608, 64)
+    blocks = sorted(set((r["desc"], r["cin_real"]) for r in recs if r["form"] == "wgrad"))
+    queries = [(what, t, c) for t, c in blocks for what in ("choice", "ws", "job")]
+    assert len(queries) >= 48
+
+    def ask(q):
+        what, t, c = q
+        d = dc.mk_desc(t)
+        if what == "choice":
+            return L.ryolo_conv_wgrad_kernel_choice(C.byref(d))
+        if what == "ws":
+            return L.ryolo_conv_wgrad_workspace_bytes(C.byref(d))
+        return dc.wgrad_plan_record(t, c)[2:]
+
+    serial = [ask(q) for q in queries]
+    codes = set(a for q, a in zip(queries, serial) if q[0] == "choice")
+    assert {256, 258, 259, 260}.issubset(codes) and any(a > dc.WGRAD_TAPS for a in codes), codes
+    assert all(a > 0 for q, a in zip(queries, serial) if q[0] == "ws")
+    assert all(a[-1] > 0 for q, a in zip(queries, serial) if q[0] == "job")         # block_end: the job was filled
+
+    PASSES = 50
+    got = {}
+    start = threading.Barrier(2)
+
+    def worker(name, order):
+        start.wait()
+        got[name] = [[ask(queries[i]) for i in order] for _ in range(PASSES)]
+
+    n = len(queries)
+    threads = [threading.Thread(target=worker, args=("up", list(range(n)))),
+               threading.Thread(target=worker, args=("down", list(range(n - 1, -1, -1))))]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    assert got["up"] == [serial] * PASSES
+    assert got["down"] == [serial[::-1]] * PASSES

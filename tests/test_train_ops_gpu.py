@@ -278,6 +278,50 @@ def test_wgrad_three_stage_tiles_equal_the_square_kernel(T, cuda_dev, n, cin, co
         assert float((out[0] - out[1]).abs().max()) <= 1e-5 * float(out[1].abs().max())
 
 
+@pytest.mark.parametrize("code,shape,tile,real", [
+    # one small case per kernel of the weight gradient's plan: (kernel code of ryolo_conv_wgrad_kernel_choice, (n, cin, cout, h, w, k, s), tile, C_in real)
+    (32, (2, 16, 48, 9, 11, 3, 1), 0, None), (64, (2, 64, 72, 9, 11, 1, 1), 0, None), (128, (2, 128, 576, 7, 9, 1, 1), 0, None),
+    (256, (2, 128, 256, 5, 5, 3, 1), 0, None),
+    (257, (2, 256, 128, 9, 9, 1, 1), 0x2000 | 0x4000, None),       # the transposed tile: behind the three-stage square one unless that is switched off
+    (258, (2, 64, 128, 5, 5, 3, 1), 0, None), (259, (2, 256, 128, 9, 9, 1, 1), 0, None), (260, (2, 128, 64, 9, 9, 1, 1), 0, None),
+    (1001, (2, 32, 64, 20, 20, 3, 1), 0, None), (1002, (2, 32, 64, 21, 17, 3, 2), 0, None), (1003, (2, 64, 32, 20, 20, 1, 1), 0, None),
+    (1004, (2, 8, 32, 20, 20, 3, 1), 0, 3)])
+def test_wgrad_phases_equal_the_one_call(T, cuda_dev, code, shape, tile, real):
+    """ryolo_conv2d_wgrad_partials followed by ryolo_conv2d_wgrad_reduce gives the bits of ryolo_conv2d_wgrad, with and without
+    accumulation, on every kernel of the plan (each case first asserts the kernel it is meant to reach); the partials call alone leaves
+    the gradient untouched."""
+    import ctypes as C
+    tr, dev = T.tr, cuda_dev
+    L = tr._lib.lib()
+    n, cin, cout, h, w, k, s = shape
+    real = real or cin
+    g = torch.Generator().manual_seed(code)
+    pad = (k - 1) // 2
+    ho, wo = (h + 2 * pad - k) // s + 1, (w + 2 * pad - k) // s + 1
+    x = torch.randn(n, h, w, cin, generator=g).to(torch.bfloat16).to(dev)
+    if real < cin:
+        x[..., real:] = 0
+    dz = torch.randn(n, ho, wo, cout, generator=g).to(torch.bfloat16).to(dev)
+    d = tr.make_desc(x, cout, k, s, pad, tile=tile)
+    assert L.ryolo_conv_wgrad_kernel_choice(C.byref(d)) == code
+    g0 = torch.randn(cout, real, k, k, generator=g).to(dev)
+    for accumulate in (True, False):
+        ws_a = torch.empty(tr.wgrad_ws_bytes(d), dtype=torch.uint8, device=dev)
+        ga = g0.clone()
+        tr.conv_wgrad(d, x, dz, real, ga, accumulate, ws_a)
+        ws_b = torch.full((tr.wgrad_ws_bytes(d),), 0x7f, dtype=torch.uint8, device=dev)           # (its own workspace, garbage on entry)
+        gb = g0.clone()
+        tr.conv_wgrad_partials(d, x, dz, real, gb, accumulate, ws_b)
+        torch.cuda.synchronize()
+        assert torch.equal(gb, g0)                        # the tile kernel alone does not touch the gradient
+        tr._lib.check(L.ryolo_conv2d_wgrad_reduce(C.byref(d), x.data_ptr(), dz.data_ptr(), dz.stride(2), real, gb.data_ptr(),
+                                                  1 if accumulate else 0, ws_b.data_ptr(), ws_b.numel(), tr._s(dev)),
+                      "ryolo_conv2d_wgrad_reduce")
+        torch.cuda.synchronize()
+        assert torch.equal(ga, gb)
+        assert not torch.equal(ga, g0)
+
+
 def test_batched_wgrad_reduce_equals_the_per_layer_reduces(T, cuda_dev):
     """ryolo_conv_wgrad_reduce_batch (round 5: the split-K reduces of a backward segment as ONE launch over a job table, every layer's
     partial tiles in its own workspace) against ryolo_conv2d_wgrad per layer: the same bits, for every reduce kind -- four split quarters

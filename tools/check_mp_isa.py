@@ -355,14 +355,14 @@ def check_conv_stem(d):
 
 
 def check_wgrad_wide(d):
-    """train.hip's wgrad_wide_kernel: three LDS stages retired by `s_waitcnt vmcnt(NLD)`.  Its direct-to-LDS loads are inline
+    """wgrad.hip's wgrad_wide_kernel: three LDS stages retired by `s_waitcnt vmcnt(NLD)`.  Its direct-to-LDS loads are inline
     assembly precisely because the compiler puts a full vmcnt(0) in front of LDS reads that follow loads it knows about; this
     fails if such a wait (or a spill) shows up between the kernel's MFMAs again."""
-    src = os.path.join(ROOT, "rotate-yolov3_amd", "csrc", "train.hip")
+    src = os.path.join(ROOT, "rotate-yolov3_amd", "csrc", "wgrad.hip")
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-value", "-save-temps",
-           "-c", src, "-o", os.path.join(d, "train.o")]
+           "-c", src, "-o", os.path.join(d, "wgrad.o")]
     subprocess.run(cmd, check=True, cwd=d, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    lines = open(os.path.join(d, "train-hip-amdgcn-amd-amdhsa-gfx950.s")).read().splitlines()
+    lines = open(os.path.join(d, "wgrad-hip-amdgcn-amd-amdhsa-gfx950.s")).read().splitlines()
     bad, found = 0, 0
     i = 0
     while i < len(lines):
@@ -398,12 +398,12 @@ def check_wgrad_wide(d):
 
 
 def check_wgrad_reduce_batch(d):
-    """train.hip's wgrad_reduce_batch_kernel (check_wgrad_wide compiled the unit): the batched split-K reduce streams at the HBM roofline only
+    """wgrad.hip's wgrad_reduce_batch_kernel (check_wgrad_wide compiled the unit): the batched split-K reduce streams at the HBM roofline only
     while every load of a split quarter is in flight at once.  A first version with a branch around each load had a compiler-inserted
     `s_waitcnt vmcnt(0)` in front of EVERY load (one round trip per split).  This fails unless the kernel holds runs of >= 15 16-B buffer
     loads (job kind 3: the 16-split pass and the 4 x 4 / 2 x 8 group passes) and a run of >= 9 4-B buffer loads (kind 4) with no vmcnt
     wait inside the run, and no scratch anywhere."""
-    lines = open(os.path.join(d, "train-hip-amdgcn-amd-amdhsa-gfx950.s")).read().splitlines()
+    lines = open(os.path.join(d, "wgrad-hip-amdgcn-amd-amdhsa-gfx950.s")).read().splitlines()
     for i, l in enumerate(lines):
         m = re.match(r"^(_ZN\S*wgrad_reduce_batch_kernel\S*):", l)
         if not m:

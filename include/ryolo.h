@@ -111,6 +111,31 @@ int ryolo_skew_iou_pairs(const float *b1, int stride1, const float *b2, int stri
 int ryolo_skew_iou_matrix(const float *b1, int n1, int stride1, const float *b2, int n2, int stride2, float *out,
                           void *stream);
 
+/* mAP matching of a whole batch -- replaces the per-image, per-prediction greedy loop of test.py:121-151 (one skew_bbox_iou call and a
+ * `detected` list per prediction) by three launches for all images of a batch.
+ *   det      [n_det, >=8] float32 rows (x, y, w, h, angle, score, class_conf, class) of all images, in image order and score-descending
+ *            inside an image (what non_max_suppression returns, concatenated); `det_stride` = floats between rows.
+ *   det_off  [n_img+1] int32: image k owns rows [det_off[k], det_off[k+1]); det_off[0] = 0, det_off[n_img] = n_det, non-decreasing.
+ *   lab      [n_lab, >=6] float32 rows (class, x, y, w, h, angle) in pixels, in image order; lab_off [n_img+1] int32 likewise.
+ *   correct  [n_det] uint8: 1 iff the reference's loop marks the prediction correct; matched [n_det] int32 (may be NULL): the row of
+ *            `lab` a correct prediction detected, -1 otherwise.
+ *   ws       ryolo_eval_match_workspace_bytes(n_det, n_lab) bytes of device scratch, 8-byte aligned (contents irrelevant on entry).
+ * Semantics: for prediction i, best(i) = the label of its image with lab class == det class (float equality) and the largest IoU, the
+ * lowest row on ties (torch.max(0)); the IoU is the fp32 value ryolo_skew_iou_matrix gives for the pair, bit for bit (the same fp64
+ * operations in the same order); i claims best(i) iff that IoU > iou_thres, compared in fp32 (`tensor > python_float` rounds the
+ * threshold to fp32); correct[i] = 1 iff i is the smallest claimant of best(i).  That IS the greedy loop: a label is marked detected only
+ * by a correct prediction whose best it is, so its first claimant finds it free and every later one finds it taken.  A NaN IoU
+ * (non-finite boxes only) makes its prediction claim nothing, as `NaN > thres` does.  No limit on predictions per image.
+ * Launches (all on `stream`, deterministic -- the only atomics are integer minima): labels -> corners, predictions -> best + atomicMin,
+ * predictions -> compare.  n_det == 0: nothing is launched; n_lab == 0: one launch writes correct = 0, matched = -1.
+ * RYOLO_EINVAL, before anything is enqueued: a negative count, det_stride < 8, lab_stride < 6, iou_thres NaN / < 0 / >= 1, workspace_bytes
+ * below the query, n_det > 0 with n_img == 0 or a null det / det_off / correct, n_det > 0 and n_lab > 0 with a null lab / lab_off or a null
+ * or misaligned ws.  The workspace query returns 0 for a negative count. */
+size_t ryolo_eval_match_workspace_bytes(int n_det, int n_lab);
+int ryolo_eval_match(const float *det, int det_stride, const int32_t *det_off, const float *lab, int lab_stride, const int32_t *lab_off,
+                     int n_img, int n_det, int n_lab, float iou_thres, uint8_t *correct, int32_t *matched /* may be NULL */, void *ws,
+                     size_t ws_bytes, void *stream);
+
 
 /* ------------------------------------------------------------------------------------------------
  * Convolution block -- replaces the operator chain the reference builds per `convolutional` cfg block,

@@ -39,6 +39,8 @@ _sigs = {
     "ryolo_rnms_count_pairs": (None, [_vp]),
     "ryolo_skew_iou_pairs": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
     "ryolo_skew_iou_matrix": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "ryolo_eval_match_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ryolo_eval_match": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp, _vp, C.c_size_t, _vp]),
     # the dry-run queries of the layer planner (model/plan.py)
     "ryolo_conv_pair_supported": (C.c_int, [_dp, _dp, C.c_int]),
     "ryolo_conv_head_decode_supported": (C.c_int, [_dp, C.c_int, C.c_int]),

@@ -1,6 +1,9 @@
 """Evaluation helpers -- mirrors of the reference's utils/utils.py: get_rotated_coors (:702-725), skew_bbox_iou (:290-320,
 here one HIP launch instead of a Python + shapely loop per pair), ap_per_class (:200-261), compute_ap (:264-286),
-scale_coords (:181-189), and the per-image greedy matching of test.py:114-151 expressed on the rotated-IoU matrix.
+scale_coords (:181-189), and the greedy matching of test.py:114-151 in two forms: `match_predictions`, the loop itself for one image on
+the rotated-IoU matrix (one launch, three host copies and a Python walk over the predictions per image), and
+`match_predictions_batched`, the same flags for all images of a batch from three launches and no host read (`ryolo_eval_match`: the
+loop restated as "a prediction is correct iff it is the first claimant of its best same-class label").
 
 Two rotated IoUs exist in the reference and both are kept, each where the reference uses it:
   * the NATIVE NMS KERNEL's fp32 arithmetic (rotate_polygon_nms_kernel.cu:22-260) -> `r_nms`, `riou_pairs`, `riou_matrix`,
@@ -13,7 +16,7 @@ import math
 import numpy as np
 import torch
 
-from .nms.r_nms import riou_matrix, riou_pairs, skew_iou_matrix, skew_iou_pairs  # noqa: F401
+from .nms.r_nms import eval_match, riou_matrix, riou_pairs, skew_iou_matrix, skew_iou_pairs  # noqa: F401
 
 
 def get_rotated_coors(box):
@@ -75,6 +78,24 @@ def match_predictions(pred, labels_px, iou_thres=0.5):
             correct[i] = 1
             detected.append(int(m[bi]))
     return correct
+
+
+def match_predictions_batched(det, det_off, targets_px, n_img, iou_thres=0.5):
+    """test.py:114-151 for a whole batch, on the device.  det [M,8] / det_off int32 [n_img+1]: the flat rows and offsets of
+    non_max_suppression_batched(..., flat=True); targets_px [nt,7] collate rows (img, cls, x, y, w, h, a) in pixels, in any row order.
+    Returns (correct uint8 [M], matched int64 [M]: the row of targets_px a correct prediction detected, else -1), both on the device;
+    correct[det_off[k]:det_off[k+1]] is match_predictions' list for image k."""
+    img = targets_px[:, 0].long()
+    order = img.argsort(stable=True)                    # loaders deliver the rows sorted by image; nothing here relies on it
+    lab = targets_px[order, 1:7].contiguous()
+    lab_off = torch.zeros(n_img + 1, dtype=torch.int32, device=targets_px.device)
+    lab_off[1:] = torch.bincount(img, minlength=n_img).cumsum(0)
+    correct, matched = eval_match(det, det_off, lab, lab_off, iou_thres)
+    hit = matched >= 0
+    matched = matched.long()
+    if len(order):
+        matched = torch.where(hit, order[matched.clamp(min=0)], matched)
+    return correct, matched
 
 
 def ap_per_class(tp, conf, pred_cls, target_cls):

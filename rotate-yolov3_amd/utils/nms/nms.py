@@ -41,34 +41,46 @@ def non_max_suppression(prediction, conf_thres=0.5, nms_thres=0.5):
     return output
 
 
-def non_max_suppression_batched(prediction, conf_thres=0.5, nms_thres=0.5):
+def _flat(output, device):
+    """(det [M, 8], det_off int32 [bs+1]) of a list of per-image rows: the rows back to back, image k in [det_off[k], det_off[k+1])"""
+    rows = [o for o in output if o is not None]
+    det = torch.cat(rows) if rows else torch.zeros(0, 8, device=device)
+    det_off = torch.tensor([0] + [0 if o is None else len(o) for o in output], dtype=torch.int32).cumsum(0, dtype=torch.int32)
+    return det, det_off.to(device)
+
+
+def non_max_suppression_batched(prediction, conf_thres=0.5, nms_thres=0.5, flat=False):
     """Same result as non_max_suppression (row for row, order included) for a GPU `prediction`, without the Python loop
     over images and classes: one vectorised filter over the whole batch, one stable (image, class, score) ordering, ONE
     segmented rotated-NMS launch over all (image, class) sets (r_nms_segmented), one final per-image score ordering.
     Three small device->host reads (candidate count, set sizes, rows per image) instead of several per image and class.
-    Like the reference it scales prediction[..., 5] by the class confidence in place (nms.py:35)."""
+    Like the reference it scales prediction[..., 5] by the class confidence in place (nms.py:35).
+    flat=True returns (output, det, det_off): besides the list, the rows of all images back to back (det [M, 8]; the list's entries are
+    slices of it) and their offsets (int32 [bs+1] on the device) -- the inputs of r_nms.eval_match, with no further host read."""
     if not prediction.is_cuda:
-        return non_max_suppression(prediction, conf_thres, nms_thres)
+        output = non_max_suppression(prediction, conf_thres, nms_thres)
+        return (output,) + _flat(output, prediction.device) if flat else output
     bs, n, no = prediction.shape
     output = [None] * bs
     if prediction.numel() == 0:
-        return output
+        return (output,) + _flat(output, prediction.device) if flat else output
     min_wh = 2
     class_conf, class_pred = prediction[..., 6:].max(2)
     prediction[..., 5] *= class_conf
     ok = (prediction[..., 5] > conf_thres) & (prediction[..., 2:4] > min_wh).all(2) & torch.isfinite(prediction).all(2)
     idx = ok.nonzero()                                            # [M, 2] (image, row), ascending     -- host read 1
     if idx.shape[0] == 0:
-        return output
+        return (output,) + _flat(output, prediction.device) if flat else output
     img, row = idx[:, 0], idx[:, 1]
     rows = prediction[img, row]                                   # [M, no]
     cand = torch.cat((rows[:, :6], class_conf[img, row].unsqueeze(1), class_pred[img, row].unsqueeze(1).float()), 1)
-    return nms_from_candidates(img, cand, bs, nms_thres, nc=no - 6)
+    return nms_from_candidates(img, cand, bs, nms_thres, nc=no - 6, flat=flat)
 
 
-def nms_from_candidates(img, cand, bs, nms_thres, nc=None):
+def nms_from_candidates(img, cand, bs, nms_thres, nc=None, flat=False):
     """Second half of non_max_suppression for a whole batch.  cand [M, 8] = (x, y, w, h, a, score, class_conf, class)
-    of the rows that passed the confidence filter, in (image, row) order; img [M] their image index."""
+    of the rows that passed the confidence filter, in (image, row) order (at least one row); img [M] their image index.
+    flat=True: (output, det, det_off) as non_max_suppression_batched describes."""
     output = [None] * bs
     cp = cand[:, 7].long()
     if nc is None:
@@ -92,10 +104,15 @@ def nms_from_candidates(img, cand, bs, nms_thres, nc=None):
     o3 = (-det[:, 5]).argsort(stable=True)
     o4 = dimg[o3].argsort(stable=True)
     det = det[o3[o4]]
-    per_img = torch.bincount(dimg, minlength=bs).tolist()         #                                    -- host read
+    counts = torch.bincount(dimg, minlength=bs)
+    per_img = counts.tolist()                                     #                                    -- host read
     start = 0
     for b, k in enumerate(per_img):
         if k:
             output[b] = det[start:start + k]
             start += k
+    if flat:
+        det_off = torch.zeros(bs + 1, dtype=torch.int32, device=det.device)
+        det_off[1:] = counts.cumsum(0)
+        return output, det, det_off
     return output

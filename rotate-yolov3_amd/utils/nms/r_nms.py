@@ -121,13 +121,39 @@ def skew_iou_matrix(box1, box2):
     return out
 
 
-def _rows(b):
+def eval_match(det, det_off, lab, lab_off, iou_thres):
+    """mAP matching of a whole batch in one call (ryolo_eval_match: three launches, no host read).  det [M, >=8] rows (x, y, w, h, a,
+    score, cls_conf, cls) of all images, image after image and score-descending inside an image; det_off int32 [n_img+1] on the device;
+    lab [T, >=6] rows (cls, x, y, w, h, a) in pixels in image order, lab_off likewise.  Returns (correct uint8 [M], matched int32 [M]: the
+    row of `lab` a correct prediction detected, else -1) on the device -- per image exactly what the greedy loop of
+    metrics.match_predictions marks."""
+    det, lab = _rows(det, 8, "det"), _rows(lab, 6, "lab")
+    m, t, n_img = det.size(0), lab.size(0), det_off.numel() - 1
+    if lab_off.numel() != n_img + 1 or n_img < 0:
+        raise RuntimeError("det_off and lab_off must both hold n_img + 1 offsets")
+    correct = torch.empty(m, dtype=torch.uint8, device=det.device)
+    matched = torch.empty(m, dtype=torch.int32, device=det.device)
+    if m == 0:
+        return correct, matched
+    det_off = det_off.to(device=det.device, dtype=torch.int32).contiguous()
+    lab_off = lab_off.to(device=det.device, dtype=torch.int32).contiguous()
+    L = _lib.lib()
+    with torch.cuda.device(det.device):
+        ws = _workspace(det.device, L.ryolo_eval_match_workspace_bytes(m, t))
+        rc = L.ryolo_eval_match(det.data_ptr(), det.stride(0), det_off.data_ptr(), lab.data_ptr(), lab.stride(0), lab_off.data_ptr(),
+                                n_img, m, t, float(iou_thres), correct.data_ptr(), matched.data_ptr(), ws.data_ptr(), ws.numel(),
+                                _lib.stream_ptr(det.device))
+    _lib.check(rc, "ryolo_eval_match")
+    return correct, matched
+
+
+def _rows(b, cols=5, what="boxes"):
     if not b.is_cuda:
-        raise RuntimeError("boxes must be a CUDAtensor ")
-    if b.dim() != 2 or b.size(1) < 5:
-        raise RuntimeError("boxes must be [N, >=5]")
+        raise RuntimeError("%s must be a CUDAtensor " % what)
+    if b.dim() != 2 or b.size(1) < cols:
+        raise RuntimeError("%s must be [N, >=%d]" % (what, cols))
     if b.dtype != torch.float32:
         b = b.float()
-    if b.stride(1) != 1 or b.stride(0) < 5:
+    if b.stride(1) != 1 or b.stride(0) < cols:
         b = b.contiguous()
     return b

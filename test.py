@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """test.py -- evaluation entry point mirroring the reference's test.py (test() :17-201, flags :205-217):
-forward (HIP engine) -> non_max_suppression -> per-image greedy matching on rotated IoU -> ap_per_class.
+forward (HIP engine) -> non_max_suppression -> greedy matching on rotated IoU -> ap_per_class.
 The reference matches predictions with a per-pair Python + shapely loop (test.py:134-151, utils/utils.py:290-320);
-here one `ryolo_riou_matrix` launch per image.  Data: synthetic loader (the OpenCV loader is out of scope)."""
+here one `ryolo_eval_match` call per batch (three launches, one device -> host transfer), or with batched_match=False one
+`ryolo_skew_iou_matrix` launch and a host loop per image.  Data: synthetic loader (the OpenCV loader is out of scope)."""
 import argparse
 import os
 import sys
@@ -15,14 +16,39 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 import rotate_yolov3_amd  # noqa: E402,F401
 from rotate_yolov3_amd.model.models import Darknet  # noqa: E402
-from rotate_yolov3_amd.utils.metrics import ap_per_class, match_predictions  # noqa: E402
+from rotate_yolov3_amd.utils.metrics import ap_per_class, match_predictions, match_predictions_batched  # noqa: E402
 from rotate_yolov3_amd.utils.nms.nms import non_max_suppression_batched as non_max_suppression  # noqa: E402  (same rows, one segmented NMS launch per batch; CPU tensors take the loop)
 from rotate_yolov3_amd.utils.parse_config import hyp_parse  # noqa: E402
 from rotate_yolov3_amd.utils.synthetic import SyntheticLoader  # noqa: E402
 
 
+def _batch_stats(stats, inf_out, targets, width, height, iou_thres, conf_thres, nms_thres):
+    """The statistics of one batch, appended to `stats` in the order of the per-image loop of test(): one NMS call, one matcher call, ONE
+    device -> host transfer (flags, scores and classes of all predictions, and below them the image and class of every target)."""
+    bs = len(inf_out)
+    output, det, det_off = non_max_suppression(inf_out, conf_thres=conf_thres, nms_thres=nms_thres, flat=True)
+    labels = targets.clone()
+    labels[:, [2, 4]] *= width
+    labels[:, [3, 5]] *= height
+    correct, _ = match_predictions_batched(det, det_off, labels, bs, iou_thres)
+    host = torch.cat((torch.stack((correct.float(), det[:, 5], det[:, 7]), 1),
+                      torch.nn.functional.pad(targets[:, :2], (0, 1))), 0).cpu()
+    rows, tgt = host[:len(det)], host[len(det):]
+    start = 0
+    for si, pred in enumerate(output):
+        tcls = tgt[tgt[:, 0] == si, 1].tolist()
+        if pred is None:
+            if tcls:
+                stats.append(([], torch.Tensor(), torch.Tensor(), tcls))
+            continue
+        r = rows[start:start + len(pred)]
+        start += len(pred)
+        stats.append((r[:, 0].long().tolist(), r[:, 1], r[:, 2], tcls))
+    return bs
+
+
 def test(cfg, hyp, weights=None, batch_size=16, img_size=608, iou_thres=0.5, conf_thres=0.001, nms_thres=0.5, model=None,
-         n_images=32, device=None, nc=None):
+         n_images=32, device=None, nc=None, batched_match=True):
     device = device or torch.device('cuda:0')
     if model is None:
         model = Darknet(cfg, hyp)
@@ -40,6 +66,9 @@ def test(cfg, hyp, weights=None, batch_size=16, img_size=608, iou_thres=0.5, con
         for imgs, targets, _, _ in SyntheticLoader(n_images, batch_size, img_size, seed=1, device=device):
             _, _, height, width = imgs.shape
             inf_out, train_out = model(imgs)
+            if batched_match:
+                seen += _batch_stats(stats, inf_out, targets, width, height, iou_thres, conf_thres, nms_thres)
+                continue
             output = non_max_suppression(inf_out, conf_thres=conf_thres, nms_thres=nms_thres)
             for si, pred in enumerate(output):
                 labels = targets[targets[:, 0] == si, 1:].clone()

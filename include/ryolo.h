@@ -218,6 +218,20 @@ int ryolo_conv_kernel_choice(const ryolo_conv_desc *desc, int with_residual, int
 #define RYOLO_WGRAD_KERNEL_TAPS 1000
 int ryolo_conv_dgrad_kernel_choice(const ryolo_conv_desc *forward_desc, int with_bn_reduce /* ryolo_conv2d_dgrad_bnreduce's choice */);
 int ryolo_conv_wgrad_kernel_choice(const ryolo_conv_desc *forward_desc);
+/* Dilated 3x3 convolution (inference, csrc/conv_dil.hip) -- replaces F.conv2d(x, module_list[s].Conv2d.weight, padding=(dil_h, dil_w),
+ * dilation=(dil_h, dil_w)), what the reference computes for a `d-convolutional` block with `weight_from = s` (model/models.py:254-267,
+ * the "matrix" cfgs): tap (r, s) of output pixel (ho, wo) reads input pixel (ho + (r-1)*dil_h, wo + (s-1)*dil_w), zero outside the
+ * image; the output is H x W.  Epilogue, arithmetic, layouts and the stream contract as for ryolo_conv2d_bn_act:
+ * y = bf16(act(acc * scale[c] + shift[c])), then bf16(y + residual) when a residual is given.  w_packed is the image
+ * ryolo_conv_pack_weights makes for the (undilated) 3x3 layer: one packed copy serves the source layer and all its sharers.
+ * Served (ryolo_conv2d_dilated_supported, no device call): ksize 3, stride 1, pad 1 (the field names the undilated window; the
+ * padding applied is the dilation), upsample 1, Cin % 64 == 0, Cout % 8 == 0, 1 <= dil_h, dil_w <= 32, act linear or leaky, channel
+ * strides multiples of 8 and at least the channel counts (res_cstride too when a residual is given), all pointers 16-byte aligned,
+ * tensors below 2 GiB.  Anything else: RYOLO_EINVAL before any HIP call.  `tile` is ignored.  One writer per output element and a
+ * fixed summation order: results are bit-identical from run to run and do not depend on the batch size. */
+int ryolo_conv2d_dilated_supported(const ryolo_conv_desc *desc, int dil_h, int dil_w);
+int ryolo_conv2d_dilated(const ryolo_conv_desc *desc, int dil_h, int dil_w, const void *x, const void *w_packed, const float *scale,
+                         const float *shift, const void *residual /* may be NULL */, void *y, void *stream);
 /* layout converters at the model boundary: the reference feeds NCHW fp32 images (train.py:236, detect.py:209) */
 int ryolo_nchw_f32_to_nhwc_bf16(const float *x, int N, int C, int H, int W, int Cpad, void *y, void *stream);
 int ryolo_nhwc_bf16_to_nchw_f32(const void *x, int N, int C, int H, int W, int cstride, float *y, void *stream);

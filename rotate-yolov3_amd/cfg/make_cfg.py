@@ -8,6 +8,9 @@ topologies are produced by code so that width/height/anchors/classes are paramet
                    (layer indices as SURVEY.md Appendix A: yolo at 82, 94, 106; routes 83, 86, 95, 98)
   darknet53_se(...)  the same with a squeeze-and-excitation block in front of every residual unit of the 256 / 512 / 1024
                    stages (the reference's cfg/ICDAR/yolov3_608_se.cfg and cfg/HRSC+/yolov3_512_se.cfg): 127 layers, 20 se
+  darknet53_matrix(...)  Darknet-53 + FPN plus the "matrix" heads of the reference's cfg/HRSC+/yolov3_512_matrix.cfg: a stride-64 head
+                   behind layer 79 and, per FPN level (layers 74 / 86 / 98), one branch per dilation that re-uses the weights of that
+                   level's head convs (weight_from) with its 3x3 convs dilated ([d-convolutional]); 16 yolo layers by default
   tiny(...)        yolov3-tiny: 13 convs, 6 maxpools, 2 yolo heads
 
     python -m rotate_yolov3_amd.cfg.make_cfg darknet53 > yolov3.cfg
@@ -74,6 +77,43 @@ def darknet53_se(width=608, height=608, anchors="ara " + ANCHORS_ARA, classes=1,
     return darknet53(width, height, anchors, classes, na_per_head, masks, se=True)
 
 
+MATRIX_DILATIONS = (((1, 2), (2, 1)),                                             # branches off layer 74 (stride 32)
+                    ((1, 2), (2, 1), (1, 4), (4, 1)),                             # layer 86 (stride 16)
+                    ((1, 2), (2, 1), (1, 4), (4, 1), (1, 8), (8, 1)))             # layer 98 (stride 8)
+
+
+def _shared(kind, filters, size, weight_from, bn=1, act="leaky", dilation=None):
+    out = ["[%s]" % kind]
+    if dilation is not None:
+        out.append("dilation=(%d,%d)" % tuple(dilation))
+    if bn:
+        out.append("batch_normalize=1")
+    return out + ["filters=%d" % filters, "size=%d" % size, "stride=1", "pad=1", "activation=%s" % act, "weight_from = %d" % weight_from, ""]
+
+
+def darknet53_matrix(width=512, height=512, anchors="ara " + ANCHORS_ARA, classes=1, na_per_head=72, dilations=MATRIX_DILATIONS):
+    """the layer graph of the reference's cfg/HRSC+/yolov3_512_matrix.cfg: layers 0-106 are darknet53(); 107-111 the stride-64 head
+    (route 79, 3x3 / 2, 1x1 with bias, head, yolo); then per level l (source layer 74 / 86 / 98, head convs l+1 .. l+7) and per dilation
+    one branch of 11 layers: route l, 1x1 (weight_from l+1), dilated 3x3 (l+2), 1x1 (l+3), dilated 3x3 (l+4), shortcut -3, 1x1 (l+5),
+    dilated 3x3 (l+6), shortcut -3, head 1x1 (l+7), yolo.  Every branch of a level uses that level's anchor mask, the stride-64 head the
+    stride-32 one; one dilation per branch (the shipped file mixes (2,1) and (1,2) inside its second branch)."""
+    no = na_per_head * (classes + 6)
+    masks = ["%d-%d" % (2 * na_per_head, 3 * na_per_head - 1), "%d-%d" % (na_per_head, 2 * na_per_head - 1), "0-%d" % (na_per_head - 1)]
+    L = darknet53(width, height, anchors, classes, na_per_head, masks).split("\n")[:-1]
+    L += ["[route]", "layers = 79", ""] + _conv(512, 3, 2) + _conv(1024, 1, 1, bn=0) + _conv(no, 1, 1, bn=0, act="linear")
+    L += _yolo(masks[0], anchors, classes)
+    for level, (src, wide) in enumerate(((74, 1024), (86, 512), (98, 256))):
+        for dil in dilations[level]:
+            L += ["[route]", "layers = %d" % src, ""]
+            for j in range(3):
+                L += _shared("convolutional", wide // 2, 1, src + 1 + 2 * j)
+                L += _shared("d-convolutional", wide, 3, src + 2 + 2 * j, dilation=dil)
+                if j:
+                    L += ["[shortcut]", "from=-3", "activation=linear", ""]
+            L += _shared("convolutional", no, 1, src + 7, bn=0, act="linear") + _yolo(masks[level], anchors, classes)
+    return "\n".join(L) + "\n"
+
+
 def tiny(width=608, height=608, anchors=TINY_PAIRS, classes=80):
     """Stock yolov3-tiny topology with the rotated head width: stock (w,h) pairs x 12 angles, comma masks index
     pairs (3,4,5 -> anchors 36..71; 1,2,3 -> 12..47), 36 anchors per head, filters = 36*(classes+6)."""
@@ -92,4 +132,4 @@ def tiny(width=608, height=608, anchors=TINY_PAIRS, classes=80):
 
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "darknet53"
-    sys.stdout.write({"darknet53": darknet53, "darknet53_se": darknet53_se, "tiny": tiny}[which]())
+    sys.stdout.write({"darknet53": darknet53, "darknet53_se": darknet53_se, "darknet53_matrix": darknet53_matrix, "tiny": tiny}[which]())

@@ -13,6 +13,9 @@ per launch.  The plan:
   * BatchNorm (eval) is folded to fp32 scale/shift applied on the fp32 accumulator (utils/torch_utils.py:45-69),
     PReLU(1)/LeakyReLU become the epilogue's slope;
   * the three YOLO decodes write straight into one [bs, sum(na*ny*nx), no] tensor (the torch.cat of models.py:298).
+  * a layer with `weight_from` (the "matrix" cfgs) is F.conv2d with its source layer's weight and nothing else (models.py:254-265): it
+    launches with the source's packed image -- packed once -- and scale 1 / shift 0; `d-convolutional` ones run ryolo_conv2d_dilated
+    (csrc/conv_dil.hip); a sharer that repeats an earlier sharer's computation aliases its tensor (RYOLO_SHARED_ALIAS=0: launches again).
   * `se` layers run ryolo_se_nhwc (csrc/se.hip: pool, gate, scale) into a buffer of their own: their input has a second reader.
 Whatever cannot be folded falls back to the small NHWC kernels of csrc/yolo.hip (add / upsample / copy / maxpool).
 All launches go to torch's current stream through the C ABI; after a warm-up the sequence can be replayed from a
@@ -64,7 +67,9 @@ class HipEngine(object):
         # ---- the plan (model/plan.py): shapes, buffers, one view per layer, the launches.  RYOLO_STEM_PAIR=0 keeps one launch per layer
         # of the Darknet-53 stem (layers 0-1 and 2-4, ryolo_conv2d_bn_act_pair), RYOLO_HEAD_DECODE=0 keeps a YOLO head's conv + decode as
         # two launches (A/B timing, tests)
-        pl = plan.plan_eval(defs, {i: self._conv_attrs(mods[i]) for i, d in enumerate(defs) if d['type'] == 'convolutional'},
+        no_alias = os.environ.get("RYOLO_SHARED_ALIAS", "1") == "0"
+        pl = plan.plan_eval(defs, {i: (dict(plan.shared_attrs(d), no_alias=no_alias) if 'weight_from' in d else self._conv_attrs(mods[i]))
+                                   for i, d in enumerate(defs) if d['type'] in plan.CONV_TYPES},
                             {i: (mods[i].na, self.no) for i in yolos}, self.bs, self.H, self.W,
                             stem_pair=os.environ.get("RYOLO_STEM_PAIR", "1") != "0",
                             head_decode=os.environ.get("RYOLO_HEAD_DECODE", "1") != "0", cin=cin)
@@ -91,7 +96,17 @@ class HipEngine(object):
         row_off = 0
         params = {}         # conv layer -> its packed weights / folded BatchNorm, in launch order
 
-        def conv_params(i, cin_k):
+        def conv_params(i, cin_k, src=None):
+            if src is not None:
+                # a weight_from layer: the source's packed image (one copy serves the source's own launch and every sharer), no BatchNorm, no bias
+                sp = conv_params(src, cin_k)
+                if 'ones' not in sp:
+                    cp = ops.cpad(sp['cout'])
+                    sp['ones'], sp['zeros'] = torch.ones(cp, device=device), torch.zeros(cp, device=device)
+                    self.keep += [sp['ones'], sp['zeros']]
+                return dict(sp, scale=sp['ones'], shift=sp['zeros'])
+            if i in params and params[i]['cin_pad'] == cin_k:
+                return params[i]
             conv, bn = self._conv_of(mods[i]), self._bn_of(mods[i])
             packed = ops.pack_weights(conv.weight.detach().float(), cin_pad=cin_k)
             if bn is not None:
@@ -106,11 +121,12 @@ class HipEngine(object):
             scale, shift = ops.pad_vec(scale, cp), ops.pad_vec(shift, cp)
             self.keep += [packed, scale, shift]
             params[i] = dict(packed=packed, scale=scale, shift=shift, cout=conv.out_channels, cin=conv.in_channels,
-                             wnumel=conv.weight.numel(), k=conv.kernel_size[0])
+                             wnumel=conv.weight.numel(), k=conv.kernel_size[0], cin_pad=cin_k)
             return params[i]
 
         def flops(i, hw):
-            return 2.0 * params[i]['k'] ** 2 * params[i]['cin'] * params[i]['cout'] * hw[1] * hw[2] * self.bs
+            pr = params[i] if isinstance(i, int) else i         # (a weight_from layer passes its source's record)
+            return 2.0 * pr['k'] ** 2 * pr['cin'] * pr['cout'] * hw[1] * hw[2] * self.bs
 
         # one scratch for every se layer: the ops are serial on one stream
         se_bytes = max([_lib.lib().ryolo_se_workspace_bytes(self.bs, op['out'].H, op['out'].W, op['C']) for op in pl.ops if op['kind'] == 'se'] or [0])
@@ -120,13 +136,21 @@ class HipEngine(object):
             kind, i = op['kind'], op['layer']
             xin, out = tv(op.get('xin')), tv(op.get('out'))
             info = dict(kind=kind, layer=i, name=kind + '_nhwc', flops=0.0)
-            if kind == 'conv':
+            if kind == 'alias':
+                continue                # this layer's tensor IS an earlier shared layer's (views[i] already says so): nothing to launch
+            if kind == 'dconv':
                 t = op['desc']
-                cv, res, ups = conv_params(i, t[3]), tv(op['res']), op['ups']
+                cv, res = conv_params(i, t[3], op['src']), tv(op['res'])
+                self.ops.append(self._mk_dconv(xin, cv, t[4], op['dil'], t[11], t[12], res, out))
+                info.update(kind='conv', name=op['name'], flops=flops(cv, shp[i]),
+                            bytes=2.0 * self.bs * (t[1] * t[2] * cv['cin'] + shp[i][1] * shp[i][2] * t[4] * (2 if res is not None else 1)) + 2.0 * cv['wnumel'])
+            elif kind == 'conv':
+                t = op['desc']
+                cv, res, ups = conv_params(i, t[3], op.get('src')), tv(op['res']), op['ups']
                 self.ops.append(self._mk_conv(xin, cv['packed'], cv['scale'], cv['shift'], t[4], t[5], t[6], t[7], t[11], t[12], res, out, ups))
                 # the kernel the library's dispatch takes for this launch (dry run of csrc/conv.hip dispatch())
                 info.update(name=ops.conv_kernel_name(*t[:8], in_cs=t[8], out_cs=t[9], res_cs=t[10], upsample=ups, residual=res is not None),
-                            flops=flops(i, shp[i]),
+                            flops=flops(cv, shp[i]),
                             bytes=2.0 * self.bs * (t[1] * t[2] * cv['cin'] + shp[i][1] * shp[i][2] * t[4] * (ups * ups + (1 if res is not None else 0)))
                             + 2.0 * cv['wnumel'])
             elif kind == 'pair':
@@ -147,10 +171,10 @@ class HipEngine(object):
                 io_bytes = self.bs * m.na * h * w * self.no * (4.0 + (4.0 if want_p else 0.0))
                 if kind == 'head':
                     # a YOLO head's conv + decode in one launch (ryolo_conv_head_decode); detect() materialises the head tensor on demand
-                    hc = dict(conv_params(op['conv'], op['desc'][3]), xin=xin)
+                    hc = dict(conv_params(op['conv'], op['desc'][3], op.get('src')), xin=xin)
                     head = dict(t=None, conv=hc, shape=(self.bs, h, w, hc['cout']))
                     self.ops.append(self._mk_head_decode(op['desc'], hc, m.na, anchors, stride, cf, row_off, pbuf))
-                    info.update(kind='conv', name='conv_pw<k1,K%d>+decode' % hc['cin'], flops=flops(op['conv'], shp[i]),
+                    info.update(kind='conv', name='conv_pw<k1,K%d>+decode' % hc['cin'], flops=flops(hc, shp[i]),
                                 bytes=2.0 * self.bs * h * w * hc['cin'] + 2.0 * hc['wnumel'] + io_bytes)
                 else:
                     head = xin
@@ -257,6 +281,11 @@ class HipEngine(object):
         def run():
             ops.conv2d_bn_act(xin, packed, scale, shift, cout, k, stride=s, pad=pad, act=act, slope=slope, residual=res,
                               out=out, upsample=ups)
+        return run
+
+    def _mk_dconv(self, xin, cv, cout, dil, act, slope, res, out):
+        def run():
+            ops.conv2d_dilated(xin, cv['packed'], cv['scale'], cv['shift'], cout, dil, act=act, slope=slope, residual=res, out=out)
         return run
 
     def _mk_add(self, a, b, out):

@@ -16,6 +16,8 @@ _lib.declare("ryolo_conv_packed_weight_bytes", C.c_size_t, [C.c_int, C.c_int, C.
 _lib.declare("ryolo_conv_pack_weights", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp])
 _lib.declare("ryolo_conv2d_bn_act", C.c_int, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp])
 _lib.declare("ryolo_conv2d_bn_act_pair", C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp])
+_lib.declare("ryolo_conv2d_dilated_supported", C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int])
+_lib.declare("ryolo_conv2d_dilated", C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
 _lib.declare("ryolo_conv_kernel_choice", C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int])
 _lib.declare("ryolo_conv_dgrad_kernel_choice", C.c_int, [C.POINTER(ConvDesc), C.c_int])
 _lib.declare("ryolo_conv_wgrad_kernel_choice", C.c_int, [C.POINTER(ConvDesc)])
@@ -84,6 +86,29 @@ def conv2d_bn_act(x, packed_w, scale, shift, cout, ksize, stride=1, pad=None, ac
                                             shift.data_ptr(), residual.data_ptr() if residual is not None else None,
                                             out.data_ptr(), _lib.stream_ptr(x.device))
     _lib.check(rc, "ryolo_conv2d_bn_act")
+    return out
+
+
+def conv2d_dilated(x, packed_w, scale, shift, cout, dil, act=ACT_LINEAR, slope=0.1, residual=None, out=None):
+    """y = act(conv3x3(x, W, padding=dil, dilation=dil) * scale + shift) + residual (csrc/conv_dil.hip); dil = (dh, dw); packed_w is the
+    image pack_weights makes for the undilated 3x3 layer; x, residual, out: NHWC bf16 (possibly slices), the output is H x W."""
+    in_cs = _check_nhwc(x, "x")
+    n, h, w, cin = x.shape
+    dh, dw = (dil, dil) if isinstance(dil, int) else dil
+    if out is None:
+        out = torch.empty((n, h, w, cout), dtype=torch.bfloat16, device=x.device)
+    out_cs = _check_nhwc(out, "out")
+    assert tuple(out.shape) == (n, h, w, cout), (tuple(out.shape), (n, h, w, cout))
+    res_cs = 0
+    if residual is not None:
+        res_cs = _check_nhwc(residual, "residual")
+        assert tuple(residual.shape) == (n, h, w, cout)
+    d = ConvDesc(n, h, w, cin, cout, 3, 1, 1, in_cs, out_cs, res_cs, act, float(slope), 1, 0)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().ryolo_conv2d_dilated(C.byref(d), int(dh), int(dw), x.data_ptr(), packed_w.data_ptr(), scale.data_ptr(),
+                                             shift.data_ptr(), residual.data_ptr() if residual is not None else None,
+                                             out.data_ptr(), _lib.stream_ptr(x.device))
+    _lib.check(rc, "ryolo_conv2d_dilated")
     return out
 
 

@@ -9,6 +9,9 @@ Same constructor, attributes and state_dict keys (`module_list.{i}.Conv2d.weight
     if libryolo_hip.so is missing this raises.
   * training-mode forward of a GPU tensor -> `TrainEngine` (model/train_engine.py): forward with batch-statistics
     BatchNorm and the matching hand-written backward (dgrad / wgrad / BN+PReLU backward), wired into autograd.
+  * blocks that carry `weight_from = s` (the "matrix" cfgs; `convolutional`, or `d-convolutional` with `dilation=(dh,dw)`) compute
+    F.conv2d(x, module_list[s].Conv2d.weight, padding, dilation) and nothing else, as models.py:254-265 does; their own modules exist for the
+    state_dict keys only.  Eval on the GPU runs them on the HIP engine (csrc/conv_dil.hip); training them needs `backend = 'torch'`.
   * a CPU tensor, or `model.backend = 'torch'` -> the same ATen operator chain the reference builds (nn.Conv2d,
     nn.BatchNorm2d, nn.PReLU, torch.cat, nn.Upsample), which is the reference's own CPU path.
 """
@@ -53,6 +56,38 @@ class SELayer(nn.Module):
         return x * y.expand_as(x)
 
 
+def parse_dilation(mdef):
+    """`dilation=(dh,dw)` of a d-convolutional block as two integers (the reference reads the single characters [1] and [3],
+    models.py:263: multi-digit values are a superset)"""
+    v = [int(t) for t in str(mdef.get('dilation', '(1,1)')).strip().strip('()').split(',')]
+    if len(v) != 2 or min(v) < 1:
+        raise ValueError('dilation=%r: expected (dh,dw) with positive integers' % (mdef.get('dilation'),))
+    return v[0], v[1]
+
+
+def shared_conv_geometry(mdef):
+    """(k, pad, dilation) of F.conv2d for a block that carries weight_from (models.py:254-265): stride 1 whatever the block says"""
+    k = int(mdef['size'])
+    if mdef['type'] == 'd-convolutional':
+        dil = parse_dilation(mdef)
+        return k, (dil if int(mdef.get('pad', 0)) else (0, 0)), dil
+    p = (k - 1) // 2 if int(mdef.get('pad', 0)) else 0
+    return k, (p, p), (1, 1)
+
+
+def _check_weight_from(i, mdef, module_defs, module_list, cin):
+    """the source of a sharing layer must be a convolutional layer that owns its weights, of the sharer's kernel size and channel counts"""
+    s = int(mdef['weight_from'])
+    what = 'layer %d (%s, weight_from = %d)' % (i, mdef['type'], s)
+    if not 0 <= s < i or module_defs[s]['type'] != 'convolutional' or 'weight_from' in module_defs[s]:
+        raise ValueError('%s: the source must be an earlier convolutional layer with its own weights' % what)
+    w = module_list[s].Conv2d.weight
+    want = (int(mdef['filters']), cin, int(mdef['size']), int(mdef['size']))
+    if tuple(w.shape) != want:
+        raise ValueError('%s: the source weight is %s, this layer needs %s (filters, incoming channels, size, size)'
+                         % (what, tuple(w.shape), want))
+
+
 def create_modules(module_defs, arc, hyp):
     """cfg dicts -> nn.ModuleList + routes (models.py:36-164).  `module_defs` loses its [net] block, as in the
     reference; the popped block is returned third."""
@@ -77,6 +112,10 @@ def create_modules(module_defs, arc, hyp):
                     print('NOTICE: layer %d filters=%d overridden to na*(nc+6)=%d for the rotated head' % (i, filters, want))
                     filters = want
                     mdef['filters'] = str(want)
+            if 'weight_from' in mdef:
+                # the block's own Conv2d / BatchNorm2d / PReLU below exist (state_dict keys as in the reference) but never run:
+                # forward computes F.conv2d with the source layer's weight and nothing else (models.py:254-265)
+                _check_weight_from(i, mdef, module_defs, module_list, output_filters[-1])
             modules.add_module('Conv2d', nn.Conv2d(in_channels=output_filters[-1], out_channels=filters,
                                                    kernel_size=kernel_size, stride=int(mdef['stride']),
                                                    padding=pad, bias=not bn))
@@ -89,6 +128,16 @@ def create_modules(module_defs, arc, hyp):
                 modules.add_module('activation', Mish())
             elif act == 'swish':
                 modules.add_module('activation', Swish())
+        elif t == 'd-convolutional' and 'weight_from' in mdef:
+            # models.py:68-77: no weights of its own (`Conv2d` is an empty Sequential); BatchNorm2d / LeakyReLU are built and never called
+            filters = int(mdef['filters'])
+            parse_dilation(mdef)
+            _check_weight_from(i, mdef, module_defs, module_list, output_filters[-1])
+            modules.add_module('Conv2d', nn.Sequential())
+            if int(mdef.get('batch_normalize', 0)):
+                modules.add_module('BatchNorm2d', nn.BatchNorm2d(filters, momentum=0.1))
+            if mdef.get('activation', 'linear') == 'leaky':
+                modules.add_module('activation', nn.LeakyReLU(0.1, inplace=True))
         elif t == 'maxpool':
             kernel_size = int(mdef['size'])
             stride = int(mdef['stride'])
@@ -134,6 +183,7 @@ def create_modules(module_defs, arc, hyp):
                     print('WARNING: smart bias initialization failure.')
             filters = output_filters[-1]
         else:
+            # (a d-convolutional block without weight_from has no weights in the reference either: its Conv2d is the empty Sequential)
             raise ValueError('Unsupported layer type in cfg: %r (d-convolutional / weight_from are out of scope, '
                              'SURVEY.md section 2)' % t)
         module_list.append(modules)
@@ -228,7 +278,10 @@ class Darknet(nn.Module):
         output = []
         for i, (mdef, module) in enumerate(zip(self.module_defs, self.module_list)):
             mtype = mdef['type']
-            if mtype in ['convolutional', 'upsample', 'maxpool', 'se']:
+            if 'weight_from' in mdef:      # convolutional / d-convolutional sharing a weight: no bias, BatchNorm or activation
+                _, pad, dil = shared_conv_geometry(mdef)
+                x = F.conv2d(x, self.module_list[int(mdef['weight_from'])].Conv2d.weight, padding=pad, dilation=dil)
+            elif mtype in ['convolutional', 'upsample', 'maxpool', 'se']:
                 x = module(x)
             elif mtype == 'route':
                 layers = [int(v) for v in mdef['layers'].split(',')]
@@ -341,6 +394,10 @@ class Darknet(nn.Module):
         """Conv+BN folding (models.py:300-313 / utils/torch_utils.py:45-69).  The HIP engine always applies the
         folded scale/shift in its conv epilogue, so there is nothing to do for it; the ATen chain is folded here."""
         from ..utils.torch_utils import fuse_conv_and_bn
+        if any('weight_from' in d for d in self.module_defs):
+            # the reference's fuse() replaces the `Conv2d` attribute its own forward looks up for the sharers: it cannot fuse these either
+            raise RuntimeError("fuse(): this cfg has weight_from layers, which read module_list[s].Conv2d.weight of their source; "
+                               "a fused model has no such attribute (the HIP engine folds BatchNorm by itself, there is nothing to fuse)")
         fused_list = nn.ModuleList()
         for a in list(self.children())[0]:
             if isinstance(a, nn.Sequential):

@@ -7,6 +7,8 @@ into the library are its dry-run queries (pair / fused head / layer-0 recompute 
 Input: the cfg `defs` (without the `net` block), batch and input size, `convs[i]` = dict(cout, k, s, pad, bn, act, slope) of
 every `convolutional` layer (the engines read them from the modules: a fused model has lost its BatchNorm modules while its
 defs still say batch_normalize=1; a `refuse` message in it is raised when the walk reaches that layer), `yolos[i]` = (na, no).
+A layer that carries `weight_from` (`convolutional` or `d-convolutional`, the matrix cfgs) is described by shared_attrs(): `src`, the
+layer whose weight it reads, `dil`, stride 1, no BatchNorm, linear -- what the reference computes for it (models.py:254-265).
 
 A `View` is a channel slice of a buffer: (buffer id, channel offset, C, H, W, pixel stride); `buffers[id]` = (C, H, W) of the
 NHWC bf16 allocation, buffer 0 is the 8-channel network input.  Two views are the same tensor exactly when they are equal.
@@ -27,6 +29,7 @@ from .._lib import ACT_LINEAR, ConvDesc
 
 View = namedtuple('View', 'buf off C H W cs')
 EvalPlan = namedtuple('EvalPlan', 'shapes buffers x views ops')
+CONV_TYPES = ('convolutional', 'd-convolutional')
 TrainPlan = namedtuple('TrainPlan', 'shapes buffers x act grd forward blocks backward')
 
 
@@ -40,6 +43,18 @@ def _abs(i, l):
 
 def _sources(i, d):
     return [_abs(i, int(v)) for v in d['layers'].split(',')]
+
+
+def shared_attrs(d):
+    """convs[i] of a block with `weight_from`: F.conv2d(x, weight of layer src, padding, dilation) and nothing else -- stride 1 whatever
+    the block says, no bias, BatchNorm or activation.  pad: 1 = "same" ((k-1)/2 * dilation per axis), 0 = none."""
+    k = int(d['size'])
+    dil = (1, 1)
+    if d['type'] == 'd-convolutional':
+        dil = tuple(int(t) for t in str(d['dilation']).strip().strip('()').split(','))
+    pad = (k - 1) // 2 if int(d.get('pad', 0)) else 0
+    return dict(cout=int(d['filters']), k=k, s=1, pad=pad, dil=dil, bn=False, act=ACT_LINEAR, slope=0.0, src=int(d['weight_from']),
+                dilated=d['type'] == 'd-convolutional', refuse=None)
 
 
 def _new(buffers, c, h, w):
@@ -57,9 +72,12 @@ def _shapes(defs, convs, cin, H, W):
     c, h, w = cin, H, W
     for i, d in enumerate(defs):
         t = d['type']
-        if t == 'convolutional':
+        if t in CONV_TYPES:
             cv = convs[i]
-            c, h, w = cv['cout'], (h + 2 * cv['pad'] - cv['k']) // cv['s'] + 1, (w + 2 * cv['pad'] - cv['k']) // cv['s'] + 1
+            dh, dw = cv.get('dil', (1, 1))
+            c = cv['cout']
+            h = (h + 2 * cv['pad'] * dh - dh * (cv['k'] - 1) - 1) // cv['s'] + 1
+            w = (w + 2 * cv['pad'] * dw - dw * (cv['k'] - 1) - 1) // cv['s'] + 1
         elif t == 'maxpool':
             k, s = int(d['size']), int(d['stride'])
             if not (k == 2 and s == 1):
@@ -136,7 +154,11 @@ def plan_eval(defs, convs, yolos, N, H, W, stem_pair=True, head_decode=True, cin
       head      layer (the yolo layer), conv, xin, desc, na, no, name
       add       layer, a, b, out            upsample  layer, xin, out, stride        maxpool   layer, xin, out, size, stride
       copy      layer (the route), xin, out  decode    layer, xin                     se        layer, xin, out, C
-    descriptors are tuples in ConvDesc field order."""
+      dconv     layer, xin, out, res, res_layer, dil, desc, name (csrc/conv_dil.hip: a dilated 3x3 with a shared weight)
+      alias     layer, of: a shared-weight layer with the input view, source and geometry of the earlier layer `of` (and no residual) IS that
+                layer's tensor -- nothing is launched (in the matrix cfgs the first 1x1 of every branch of a level)
+    conv / dconv / head ops of a layer with `weight_from` carry src = the layer whose packed weight they read (scale 1, shift 0); the
+    others have src None.  descriptors are tuples in ConvDesc field order."""
     n = len(defs)
     shp = _shapes(defs, convs, cin, H, W)
     for i, d in enumerate(defs):
@@ -148,7 +170,7 @@ def plan_eval(defs, convs, yolos, N, H, W, stem_pair=True, head_decode=True, cin
     fused_into = {}     # follower layer (shortcut / upsample) -> conv layer that computes it
     conv_res, conv_ups = {}, set()
     for i, d in enumerate(defs):
-        if i == 0 or defs[i - 1]['type'] != 'convolutional' or readers[i - 1] != [i] or (i - 1) in fused_into.values():
+        if i == 0 or defs[i - 1]['type'] not in CONV_TYPES or readers[i - 1] != [i] or (i - 1) in fused_into.values():
             continue
         if d['type'] == 'shortcut' and _abs(i, int(d['from'])) != i - 1:
             fused_into[i] = i - 1
@@ -166,7 +188,7 @@ def plan_eval(defs, convs, yolos, N, H, W, stem_pair=True, head_decode=True, cin
     for i, srcs in concat.items():
         views[i] = _new(buffers, *shp[i])
         for src, off in srcs:
-            if src not in home and defs[src]['type'] in ('convolutional', 'shortcut', 'upsample', 'maxpool', 'se') and src < i \
+            if src not in home and defs[src]['type'] in CONV_TYPES + ('shortcut', 'upsample', 'maxpool', 'se') and src < i \
                     and shp[src][0] % 8 == 0 and off % 8 == 0:
                 home[src] = _slice(views[i], off, shp[src][0])
             else:
@@ -176,6 +198,7 @@ def plan_eval(defs, convs, yolos, N, H, W, stem_pair=True, head_decode=True, cin
         return home[i] if i in home else _new(buffers, *shp[i])
 
     ops = []
+    shared_seen = {}     # (input view, source layer, k, pad, dilation) -> the shared-weight layer that already computed it
     pending = None       # first layer of a fused stem pair, waiting for its successor
     pending_head = None  # last conv of a YOLO head, emitted together with its decode
     for i, d in enumerate(defs):
@@ -183,10 +206,11 @@ def plan_eval(defs, convs, yolos, N, H, W, stem_pair=True, head_decode=True, cin
         if i in fused_into:
             views[i] = views[fused_into[i]]        # the conv already produced this layer's tensor
             continue
-        if t == 'convolutional':
+        if t in CONV_TYPES:
             cv = convs[i]
             if cv.get('refuse'):
                 raise Refused(cv['refuse'])
+            src = cv.get('src')                    # the layer whose weight a `weight_from` layer reads
             xin = x if i == 0 else views[i - 1]    # (None behind the first layer of a fused pair)
             cin_k = convs[pending['layer']]['cout'] if pending is not None else xin.C
             res = views[conv_res[i]] if i in conv_res else None
@@ -203,6 +227,32 @@ def plan_eval(defs, convs, yolos, N, H, W, stem_pair=True, head_decode=True, cin
                                 descs=pair_descs(N, first['xin'], fc, cv, out.cs),
                                 name='conv_stem_pair<k%ds%d+k%ds%d%s>' % (fc['k'], fc['s'], cv['k'], cv['s'], '+res' if res is not None else '')))
                 continue
+            if src is not None:
+                key = (xin, src, cv['k'], cv['pad'], cv['dil'])
+                if res is None and ups == 1 and i not in home and key in shared_seen and not cv.get('no_alias'):
+                    views[i] = views[shared_seen[key]]
+                    ops.append(dict(kind='alias', layer=i, of=shared_seen[key]))
+                    continue
+            if cv.get('dilated'):
+                # csrc/conv_dil.hip: 3x3, "same" padding, C_in a multiple of 64; the output never overlaps the input it reads around
+                views[i] = out = view_for(final)
+                desc = (N, xin.H, xin.W, xin.C, cv['cout'], cv['k'], 1, cv['pad'], xin.cs, out.cs, res.cs if res is not None else 0,
+                        cv['act'], cv['slope'], 1, 0)
+                if cv['pad'] == 0 or cv['k'] != 3:
+                    raise Refused("d-convolutional %d: only size=3 with pad=1 (padding = dilation) is on the HIP path" % i)
+                if xin.C % 64:
+                    raise Refused("d-convolutional %d: %d input channels (the dilated kernel serves multiples of 64)" % (i, xin.C))
+                if ups != 1:
+                    raise Refused("d-convolutional %d: no fused upsample" % i)
+                if out.buf == xin.buf and out.off < xin.off + xin.C and xin.off < out.off + out.C:
+                    raise Refused("d-convolutional %d: its route home would make it write the tensor it reads (in place)" % i)
+                if not _query('ryolo_conv2d_dilated_supported', desc, int(cv['dil'][0]), int(cv['dil'][1])):
+                    raise Refused("d-convolutional %d: dilation %s / shape not served by ryolo_conv2d_dilated" % (i, (cv['dil'],)))
+                if res is None and i not in home:
+                    shared_seen.setdefault(key, i)
+                ops.append(dict(kind='dconv', layer=i, xin=xin, out=out, res=res, res_layer=conv_res.get(i), dil=tuple(cv['dil']), desc=desc,
+                                src=src, name='conv_dil<d%dx%d%s>' % (cv['dil'][0], cv['dil'][1], '+res' if res is not None else '')))
+                continue
             alone = readers[i] == [i + 1] and i not in home and res is None and ups == 1
             if (head_decode and alone and not cv['bn'] and cv['act'] == ACT_LINEAR and cv['k'] == 1 and cv['s'] == 1 and
                     defs[i + 1]['type'] == 'yolo'):
@@ -210,9 +260,9 @@ def plan_eval(defs, convs, yolos, N, H, W, stem_pair=True, head_decode=True, cin
                 na, no = yolos[i + 1]
                 ht = (N, xin.H, xin.W, xin.C, cv['cout'], 1, 1, 0, xin.cs, cv['cout'], 0, ACT_LINEAR, 0.0, 1, 0)
                 if _query('ryolo_conv_head_decode_supported', ht, int(na), int(no)):
-                    pending_head = dict(kind='head', conv=i, xin=xin, desc=ht, na=na, no=no, name='conv_pw<k1,K%d>+decode' % xin.C)
+                    pending_head = dict(kind='head', conv=i, xin=xin, desc=ht, na=na, no=no, name='conv_pw<k1,K%d>+decode' % xin.C, src=src)
                     continue
-            if (stem_pair and alone and i not in conv_res and defs[i + 1]['type'] == 'convolutional' and (i + 1) not in conv_ups
+            if (stem_pair and alone and src is None and i not in conv_res and defs[i + 1]['type'] == 'convolutional' and (i + 1) not in conv_ups
                     and convs[i + 1]['bn']):
                 nx = convs[i + 1]
                 if nx.get('refuse'):
@@ -226,7 +276,9 @@ def plan_eval(defs, convs, yolos, N, H, W, stem_pair=True, head_decode=True, cin
             views[i] = out = view_for(final)
             desc = (N, xin.H, xin.W, xin.C, cv['cout'], cv['k'], cv['s'], cv['pad'], xin.cs, out.cs, res.cs if res is not None else 0,
                     cv['act'], cv['slope'], ups, 0)
-            ops.append(dict(kind='conv', layer=i, xin=xin, out=out, res=res, res_layer=conv_res.get(i), ups=ups, desc=desc))
+            if src is not None and res is None and ups == 1 and i not in home:
+                shared_seen.setdefault(key, i)
+            ops.append(dict(kind='conv', layer=i, xin=xin, out=out, res=res, res_layer=conv_res.get(i), ups=ups, desc=desc, src=src))
         elif t == 'shortcut':
             views[i] = view_for(i)
             ops.append(dict(kind='add', layer=i, a=views[i - 1], b=views[_abs(i, int(d['from']))], out=views[i]))
@@ -271,6 +323,9 @@ def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, 
     blocks: the conv records.  backward: (kind, layer, flags) in launch order (forward reversed); flags say which gradient views the
     entry is the FIRST to write (it overwrites, later ones accumulate): conv (res_g, xin_g), add (a_g, b_g), up x_g; yolo: head index."""
     n = len(defs)
+    if any(d['type'] == 'd-convolutional' or 'weight_from' in d for d in defs):
+        # a sharer would train as a layer with weights of its own, BatchNorm and activation: a different network
+        raise Refused("training path: weight_from / d-convolutional layers have no HIP training kernels (use model.backend = 'torch')")
     shp = _shapes(defs, convs, cin, H, W)
     for i, d in enumerate(defs):
         if d['type'] == 'upsample' and int(d['stride']) != 2:

@@ -274,6 +274,13 @@ int ryolo_conv_head_decode_supported(const ryolo_conv_desc *desc, int na, int no
 int ryolo_conv_head_decode(const ryolo_conv_desc *desc, const void *x, const void *w_packed, const float *scale, const float *shift,
                            const float *anchors, int na, int no, float stride, float context_factor, int arc, float *io,
                            long long io_rows_per_image, long long io_row_offset, float *p, void *stream);
+/* The training form of the same launch (served for the shapes ryolo_conv_head_decode_supported accepts): the training forward needs
+ * the raw head values p [bs, na, ny, nx, no] fp32 (the p-only form of ryolo_yolo_decode) AND the bf16 head tensor itself, which the
+ * loss and the backward read.  The on-chip head tile is written out twice -- as p rows and as NHWC rows of `head` (pixel stride
+ * head_cstride, a multiple of 8; channels >= C_out are not touched) -- instead of being stored by the conv and re-read by the decode.
+ * head and p are bit-identical to ryolo_conv2d_bn_act + ryolo_yolo_decode. */
+int ryolo_conv_head_decode_store(const ryolo_conv_desc *desc, const void *x, const void *w_packed, const float *scale, const float *shift,
+                                 int na, int no, void *head, int head_cstride, float *p, void *stream);
 
 /* NHWC bf16 helpers for cfg graphs whose shortcut / upsample / route / maxpool cannot be fused into a conv
  * epilogue (model/models.py:79-94, :269-282).  Channel counts and strides multiples of 8. */
@@ -518,6 +525,27 @@ int ryolo_yolo_loss_nhwc_arc(const void *head, int head_cstride, const float *p,
                              int iou_mode, int arc, float fl_gamma, unsigned *bitmap, float *dp_sparse, void *head_grad,
                              int head_grad_cstride, float *items, void *stream);
 int ryolo_scale_bf16_if(const float *g, void *buf, int cstride, long long npix, int C, void *stream);
+/* The head conv's bias gradient out of the loss's dense pass ('default' arc, C = na*no <= 512).  ryolo_yolo_loss_nhwc_bias is
+ * ryolo_yolo_loss_nhwc_arc whose dense kernel also sums, per channel, the bf16 head-gradient values it stores (the positives merged)
+ * and writes rows of partial sums: bias_part [ryolo_yolo_loss_bias_rows(...)][bias_cstride] fp32, C <= bias_cstride <= 512, a multiple
+ * of 8; every row is written, the buffer needs no clearing.  bias_part NULL: exactly ryolo_yolo_loss_nhwc_arc.  The rows query returns 0
+ * where the fold is not served.  head_grad is byte-identical with and without bias_part.
+ * ryolo_head_bias_finalize (npix = bs*ny*nx): dbias[c] += g[0] * sum over rows.  Rows and finalize add in the order of ryolo_bn_act_bwd's
+ * bias form (scale == NULL) over the head gradient -- ryolo_bn_act_bwd_bias_order: its slabs and pixel lanes; a row is one pixel lane of
+ * one slab -- so for g[0] == 1 dbias receives the same bits (no atomics anywhere).  g: the device scalar of the upstream gradient (the
+ * rows hold the unscaled sums; the separate pass sums the values ryolo_scale_bf16_if scaled and rounded: equal for powers of two).
+ * workspace: ryolo_head_bias_workspace_bytes(npix, C). */
+int ryolo_bn_act_bwd_bias_order(long long npix, int C, long long *slab_pixels, int *pixel_lanes);   /* returns the number of slabs */
+int ryolo_yolo_loss_bias_rows(int bs, int na, int ny, int nx, int no, int arc);
+int ryolo_yolo_loss_nhwc_bias(const void *head, int head_cstride, const float *p, int bs, int na, int ny, int nx, int no, int nc,
+                              const float *w, int NT, const long long *b, const long long *gj, const long long *gi,
+                              const long long *cls, const float *txy, const float *twh, const float *ta, const float *anchor_vec,
+                              const float *npos, float giou, float reg_w, float cls_w, float cls_pw, float obj_w, float obj_pw,
+                              int iou_mode, int arc, float fl_gamma, unsigned *bitmap, float *dp_sparse, void *head_grad,
+                              int head_grad_cstride, float *items, float *bias_part, int bias_cstride, void *stream);
+size_t ryolo_head_bias_workspace_bytes(long long npix, int C);
+int ryolo_head_bias_finalize(const float *bias_part, long long npix, int bias_cstride, int C, const float *g, float *dbias, void *workspace,
+                             size_t workspace_bytes, void *stream);
 
 /* Rotated IoU of n box pairs (cx, cy, w, h, angle; angle convention of get_rotated_coors, utils/utils.py:702-725) and its
  * gradient with respect to the FIRST box: iou [n], grad [n,5] (may be NULL).  The value is the polygon IoU of

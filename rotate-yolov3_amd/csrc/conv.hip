@@ -1782,6 +1782,15 @@ int ryolo_conv_head_decode(const ryolo_conv_desc *d, const void *x, const void *
     return launch_conv_pw_decode(p, io, io_rows_per_image, io_row_offset, pout, anchors, na, no, stride, context_factor, arc, (hipStream_t)stream_);
 }
 
+int ryolo_conv_head_decode_store(const ryolo_conv_desc *d, const void *x, const void *w_packed, const float *scale, const float *shift,
+                                 int na, int no, void *head, int head_cstride, float *pout, void *stream_) {
+    ConvParams p{};
+    if (!x || !w_packed || !scale || !shift || !head || !pout || !head_params(d, p) || !conv_pw_decode_supported(p, na, no)) return RYOLO_EINVAL;
+    if (((uintptr_t)x | (uintptr_t)w_packed) & 15) return RYOLO_EINVAL;
+    p.x = (const __bf16 *)x; p.w = (const __bf16 *)w_packed; p.scale = scale; p.shift = shift;
+    return launch_conv_pw_decode(p, nullptr, 0, 0, pout, nullptr, na, no, 1.f, 1.f, 0, (hipStream_t)stream_, head, head_cstride);
+}
+
 int ryolo_conv_pair_supported(const ryolo_conv_desc *first, const ryolo_conv_desc *second, int shortcut_from_input) {
     if (conv_validate(first) != RYOLO_OK || conv_validate(second) != RYOLO_OK) return 0;
     return conv_stem_pair_kind(first, second, shortcut_from_input) != 0 ? 1 : 0;

@@ -109,6 +109,9 @@ struct PwBnRed {
 // to an LDS tile [rows][channels] instead of HBM, and the workgroup decodes them there -- YOLOLayer.forward (model/models.py:183-227),
 // the arithmetic of yolo.hip's decode kernels (shared header) -- writing the io / p rows.  The head tensor (186 MB at 76^2, bs 32) is
 // neither written nor re-read.
+// MODE 5 (training forward): the same head tile leaves as the raw p rows AND as NHWC rows of the bf16 head tensor (the loss and the
+// backward read it) -- no io rows, no decode arithmetic.  The conv's store of the head and the decode pass's re-read of it become one
+// store from LDS.
 struct PwDecode {
     float *io, *p;          // [bs][io_img_rows][no] (+ row offset io_row0), [bs][na][ny][nx][no]; p may be null
     const float *anchors;   // [na][3]
@@ -117,6 +120,9 @@ struct PwDecode {
     float stride, cf;
     int arc;
     int apb;                // anchors per channel block: block nb computes channels nb*apb*no .. + 255 and decodes anchors nb*apb .. + apb - 1
+    __bf16 *head;           // MODE 5: [M][head_cs] bf16, channels 0 .. C_out - 1 of every pixel are written; null: MODE 4
+    int head_cs;
+    unsigned head_bytes;
 };
 
 template <int KT, int NW, int CF, int PF, int RING, int MODE>
@@ -125,7 +131,7 @@ __global__ void __launch_bounds__(NW * 64, 2) conv_pw_kernel(const ConvParams p,
     constexpr int UNIT = BMS * 128;              // bytes of one unit (BMS rows x 64 channels)
     constexpr int LPU = (BMS / 8) / NW;          // 1-KiB direct-to-LDS pieces a wave issues per unit
     constexpr int NCB = NW * CF * 16;            // output channels of a workgroup
-    constexpr bool HAS_RES = MODE == 2 || MODE == 3, BNRED = MODE == 3, STATS = MODE == 1, DEC = MODE == 4;
+    constexpr bool HAS_RES = MODE == 2 || MODE == 3, BNRED = MODE == 3, STATS = MODE == 1, DEC = MODE == 4 || MODE == 5, HEADST = MODE == 5;
     constexpr int TROW = NCB * 2 + 16;           // DEC: byte pitch of a row of the head tile (the 16-B pad spreads the rows over the banks)
     constexpr int NSTG = DEC ? 0 : (CF == 2 ? PF : PF / 2);  // 16-B output runs (= stores, accumulate loads, z loads) per lane and row block
                                                  // (DEC: the decode stage's stores are not counted: the waits then allow fewer operations in
@@ -373,6 +379,33 @@ __global__ void __launch_bounds__(NW * 64, 2) conv_pw_kernel(const ConvParams p,
                 __syncthreads();      // (drains this wave's look-ahead fills too: once per row block, behind 4-16 K steps of MFMAs)
                 const int a0 = nb * dc.apb, na_here = min(dc.apb, dc.na - a0);
                 const int nrows = BMS * na_here;
+                if constexpr (HEADST) {
+#if defined(__HIP_DEVICE_COMPILE__)
+                    // The tile's rows -> the head tensor.  This block owns channels c_lo .. c_hi - 1 (its anchors; c_lo = n0 is even, a
+                    // multiple of 8 only for block 0): whole 8-channel chunks inside the range leave as 16-B stores, the up to three
+                    // channel pairs at either end as 4-B stores -- the neighbouring block writes the rest of those chunks.
+                    const __amdgpu_buffer_rsrc_t hrs = __builtin_amdgcn_make_buffer_rsrc((void *)dc.head, 0, dc.head_bytes, 0x00020000);
+                    const int c_lo = n0, c_hi = n0 + na_here * dc.no;
+                    const int a_lo = (c_lo + 7) & ~7, a_hi = max(c_hi & ~7, a_lo);
+                    const int nch = (a_hi - a_lo) >> 3;
+                    for (int idx = tid; idx < BMS * nch; idx += NW * 64) {
+                        const int pxl = idx / nch, ch = a_lo + (idx - pxl * nch) * 8;
+                        const int m = m0 + pxl;
+                        if (m >= p.M) continue;
+                        const unsigned *src = (const unsigned *)(tile + pxl * TROW + (ch - n0) * 2);
+                        __builtin_amdgcn_raw_buffer_store_b128(u32x4{src[0], src[1], src[2], src[3]}, hrs, (m * dc.head_cs + ch) * 2, 0, 0);
+                    }
+                    const int nl = (a_lo - c_lo) >> 1, ne = nl + ((c_hi - a_hi) >> 1);
+                    for (int idx = tid; idx < BMS * ne; idx += NW * 64) {
+                        const int pxl = idx / ne, j = idx - pxl * ne;
+                        const int ch = j < nl ? c_lo + 2 * j : a_hi + 2 * (j - nl);
+                        const int m = m0 + pxl;
+                        if (m >= p.M) continue;
+                        const unsigned *src = (const unsigned *)(tile + pxl * TROW + (ch - n0) * 2);
+                        __builtin_amdgcn_raw_buffer_store_b32(src[0], hrs, (m * dc.head_cs + ch) * 2, 0, 0);
+                    }
+#endif
+                }
                 const long long hw = (long long)dc.ny * dc.nx;
                 for (int rw = tid; rw < nrows; rw += NW * 64) {
                     const int al = rw / BMS, pxl = rw - al * BMS;           // rows of one anchor over consecutive pixels: adjacent in io / p
@@ -390,8 +423,10 @@ __global__ void __launch_bounds__(NW * 64, 2) conv_pw_kernel(const ConvParams p,
                         if (k < dc.no) v[k] = (float)src[k];
                     const long long row = (long long)a * hw + (long long)y * dc.nx + x;
                     if (dc.p) store_row(dc.p + (((long long)n * dc.na * hw) + row) * dc.no, v, dc.no);
-                    const float aw = dc.anchors[a * 3 + 0] / dc.stride, ah = dc.anchors[a * 3 + 1] / dc.stride, aa = dc.anchors[a * 3 + 2];
-                    decode_row<8>(v, dc.no, x, y, aw, ah, aa, dc.stride, dc.cf, dc.arc, dc.io + (((long long)n * dc.io_img_rows) + dc.io_row0 + row) * dc.no);
+                    if constexpr (!HEADST) {
+                        const float aw = dc.anchors[a * 3 + 0] / dc.stride, ah = dc.anchors[a * 3 + 1] / dc.stride, aa = dc.anchors[a * 3 + 2];
+                        decode_row<8>(v, dc.no, x, y, aw, ah, aa, dc.stride, dc.cf, dc.arc, dc.io + (((long long)n * dc.io_img_rows) + dc.io_row0 + row) * dc.no);
+                    }
                 }
                 return;
             }
@@ -543,7 +578,7 @@ static thread_local const PwDecode *g_pw_decode = nullptr;      // set around th
 
 template <int KT, int NW, int CF, int PF, int RING, int MODE>
 int pw_launch(ConvParams &p, const PwBnRed &br, int grid, hipStream_t stream) {
-    constexpr int LDS = RING * PF * 16 * 128 + (MODE == 4 ? PF * 16 * (NW * CF * 16 * 2 + 16) : 0);
+    constexpr int LDS = RING * PF * 16 * 128 + (MODE == 4 || MODE == 5 ? PF * 16 * (NW * CF * 16 * 2 + 16) : 0);
     const PwDecode dc = g_pw_decode ? *g_pw_decode : PwDecode{};
     return launch_kernel<conv_pw_kernel<KT, NW, CF, PF, RING, MODE>>(dim3((unsigned)grid), dim3(NW * 64), LDS, stream, p, br, dc);
 }
@@ -552,7 +587,8 @@ int pw_launch(ConvParams &p, const PwBnRed &br, int grid, hipStream_t stream) {
 template <int KT, int NW, int CF, int PF, int RING, int MODES>
 int pw_launch_mode(ConvParams &p, const PwBnRed *br, int grid, hipStream_t stream) {
     PwBnRed none{};
-    const int mode = g_pw_decode ? 4 : (br ? 3 : (p.stat_part ? 1 : (p.res ? 2 : 0)));
+    const int mode = g_pw_decode ? (g_pw_decode->head ? 5 : 4) : (br ? 3 : (p.stat_part ? 1 : (p.res ? 2 : 0)));
+    if constexpr ((MODES & 32) != 0) if (mode == 5) return pw_launch<KT, NW, CF, PF, RING, 5>(p, none, grid, stream);
     if constexpr ((MODES & 16) != 0) if (mode == 4) return pw_launch<KT, NW, CF, PF, RING, 4>(p, none, grid, stream);
     if constexpr ((MODES & 8) != 0) if (mode == 3) return pw_launch<KT, NW, CF, PF, RING, 3>(p, *br, grid, stream);
     if constexpr ((MODES & 2) != 0) if (mode == 1) return pw_launch<KT, NW, CF, PF, RING, 1>(p, none, grid, stream);
@@ -646,11 +682,20 @@ static int pw_decode_apb(int na, int no, int ncb = 256) {
 
 // the head conv + decode as one launch (conv.hip: ryolo_conv_head_decode); EINVAL when the shape is not served
 int launch_conv_pw_decode(ConvParams &p, float *io, long long io_img_rows, long long io_row0, float *pout, const float *anchors, int na, int no,
-                          float stride, float cf, int arc, hipStream_t stream) {
-    if (!io || !anchors || na <= 0 || no < 7 || no > 8 || na * no != p.Cout || p.ups != 1 || p.res || p.stat_part) return RYOLO_EINVAL;
+                          float stride, float cf, int arc, hipStream_t stream, void *head, int head_cs) {
+    if (na <= 0 || no < 7 || no > 8 || na * no != p.Cout || p.ups != 1 || p.res || p.stat_part) return RYOLO_EINVAL;
+    // inference: io rows (+ p); training (head != null): p rows + the head tensor, no io
+    if (head ? (!pout || io) : (!io || !anchors)) return RYOLO_EINVAL;
     const long long dmax = p.Wo > p.Ho ? p.Wo : p.Ho;
     if (((long long)p.M + 64) * dmax >= 0x100000000ll) return RYOLO_EINVAL;       // the multiply-high pixel decomposition must be exact
     PwDecode dc;
+    dc.head = (__bf16 *)head; dc.head_cs = head_cs; dc.head_bytes = 0;
+    if (head) {
+        // 16-B stores of whole 8-channel chunks, 4-B stores of channel pairs: C_out and the pixel stride multiples of 8, 32-bit byte offsets
+        const unsigned long long hb = (((unsigned long long)p.M - 1) * (unsigned long long)head_cs + p.Cout) * 2ull;
+        if ((p.Cout & 7) || (head_cs & 7) || head_cs < p.Cout || ((uintptr_t)head & 15) || hb >= 0x7fffff00ull) return RYOLO_EINVAL;
+        dc.head_bytes = (unsigned)hb;
+    }
     dc.io = io; dc.p = pout; dc.anchors = anchors; dc.io_img_rows = io_img_rows; dc.io_row0 = io_row0;
     dc.na = na; dc.no = no; dc.ny = p.Ho; dc.nx = p.Wo; dc.stride = stride; dc.cf = cf; dc.arc = arc;
     dc.apb = pw_decode_apb(na, no, p.Cin == 1024 ? 128 : 256);
@@ -728,12 +773,12 @@ int launch_conv_pw(ConvParams &p, const ConvLaunch &lc) {
     PW_CASE(4, 4, 2, 8, 4, 3)      // (no accumulate-operand instantiation: it needs 12 spilled registers inside the loop; such launches take the 128x128 tile)
     PW_CASE(6, 4, 2, 4, 8, 7)
     PW_CASE(2, 8, 2, 4, 12, 15)
-    PW_CASE(4, 8, 2, 4, 12, 23)
+    PW_CASE(4, 8, 2, 4, 12, 55)
     PW_CASE(4, 8, 1, 4, 12, 8)
-    PW_CASE(8, 8, 2, 4, 12, 23)
+    PW_CASE(8, 8, 2, 4, 12, 55)
     PW_CASE(8, 8, 1, 4, 12, 8)
     PW_CASE(12, 8, 1, 4, 12, 7)
-    PW_CASE(16, 8, 1, 4, 12, 23)
+    PW_CASE(16, 8, 1, 4, 12, 55)
 #undef PW_CASE
     return RYOLO_EINVAL;
 }

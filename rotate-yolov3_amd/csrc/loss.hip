@@ -253,15 +253,38 @@ __global__ void __launch_bounds__(256) yolo_loss_pos_kernel(const PosParams q) {
 // a*no + k -- the same values as p) and writes the head gradient in the layout the backward consumes: objectness column
 // coef * sigmoid(x), every other entry 0, plus -- for the few cells the positives kernel touched (bitmap) -- its fp32
 // contributions, which are read from the sparse buffer `dp` and ZEROED again, so that buffer stays all-zero between steps.
+//
+// FOLD (the head conv has a bias and C <= 512, so a lane keeps ONE 8-channel chunk for the whole launch): the kernel also sums, per
+// channel, the gradient values it stores -- the bf16-rounded ones, positives merged, which is what a separate pass over `hg` would
+// read: the head's bias gradient without re-reading the head gradient (csrc/train.hip: ryolo_head_bias_finalize).  The sums are taken
+// IN THE ORDER of that separate pass (bn_act_bwd_reduce_kernel, bias form), so the bias gradient keeps its bits: that pass cuts the
+// pixels into slabs of `slab` pixels and gives pixel lane l of `npl` the pixels slab start + l, + npl, ... of its slab, added one after
+// the other.  Here a WAVE is such a (slab, pixel lane) stream -- wave index = slab * npl + l -- and writes its sums as row
+// bias_part[wave index][bias_cs]; the finalize adds a slab's lanes and then the slabs as the separate pass's kernels do.  No atomics.
 typedef __attribute__((ext_vector_type(8))) __bf16 loss_bf16x8;
-template <int NO>
-__global__ void __launch_bounds__(256)
+constexpr int BIAS_FOLD_CMAX = 512;
+// (waves_per_eu: the FOLD variant keeps its stream bounds in scalar registers and would take 103 of them, one wave of occupancy --
+//  and with a wave per stream the 76^2 head has exactly as many streams as the chip holds waves at eight per SIMD)
+template <int NO, bool FOLD = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
 yolo_loss_dense_nhwc_kernel(const __bf16 *__restrict__ head, int head_cs, long long npix, int plane, int na, int no_rt, float coef,
                             float *__restrict__ dp, const unsigned *__restrict__ bitmap, __bf16 *__restrict__ hg, int hg_cs,
-                            float *__restrict__ items) {
+                            float *__restrict__ items, float *__restrict__ bias_part = nullptr, int bias_cs = 0, int bias_rows = 0,
+                            int slab = 1, int npl = 1) {
     const int no = NO ? NO : no_rt;
     const int cpr = na * no / 8;
     float acc = 0.f;
+    // FOLD: sums of the stored values of this lane's chunk.  Only the (at most two) objectness channels, whose positions are the same
+    // for every pixel, receive a non-zero value at every pixel: two registers.  The other channels are non-zero only in a chunk with
+    // positives (rare): they are added in the lane's own eight floats of an LDS row (adding the exact zeros of all other pixels
+    // would change nothing, so the order of the separate pass is kept).
+    __shared__ __attribute__((aligned(16))) float bred[FOLD ? 4 : 1][FOLD ? BIAS_FOLD_CMAX : 1];
+    float bobj1 = 0.f, bobj2 = 0.f;
+    const int brow = FOLD ? (int)(threadIdx.x & 63) * 8 : 0;      // the lane's eight floats of its wave's LDS row
+    if constexpr (FOLD) {
+#pragma unroll
+        for (int e = 0; e < 8; e++) bred[threadIdx.x >> 6][brow + e] = 0.f;
+    }
     // A wave owns one pixel per trip (lane = 16-B chunk of its channels, 64 chunks per sweep).  The pass was ALU-bound twice over:
     // the first version decomposed a flat index with two 64-bit divisions per chunk (~250 instructions per 16 bytes moved); the
     // second tested `column == 5` per element, and with 63 lanes in 7 different phases every element's sigmoid / softplus / IEEE
@@ -269,7 +292,10 @@ yolo_loss_dense_nhwc_kernel(const __bf16 *__restrict__ head, int head_cs, long l
     // objectness columns (one when no >= 8) at positions known from its first column: they are selected, evaluated once each, and
     // scattered back; the positives' contributions (rare) take a wave-divergent slow path.
     const int lane = threadIdx.x & 63;
-    const long long wave0 = (long long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long long)gridDim.x * 4;
+    // (FOLD: the wave index as a scalar, so the stream's bounds and the pixel counter live in scalar registers -- the fold's sums must not
+    //  cost the pass a wave of occupancy)
+    const int wv = FOLD ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
+    const long long wave0 = (long long)blockIdx.x * 4 + wv, nwaves = (long long)gridDim.x * 4;
     auto one = [&](long long pix, int c8, const loss_bf16x8 &v) {
         const int a0 = c8 / no, k0 = c8 - a0 * no;       // anchor / column of the chunk's first channel
         int e1 = 5 - k0;
@@ -327,14 +353,60 @@ yolo_loss_dense_nhwc_kernel(const __bf16 *__restrict__ head, int head_cs, long l
                     j++;
                 }
             }
+            if constexpr (FOLD) {                        // the eight values as stored
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    const float q = __builtin_bit_cast(float, (e & 1) ? (ow[e >> 1] & 0xffff0000u) : (ow[e >> 1] << 16));
+                    if (e == e1) bobj1 += q;
+                    else if (e == e2) bobj2 += q;
+                    else bred[threadIdx.x >> 6][brow + e] += q;
+                }
+            }
+        } else if constexpr (FOLD) {
+            bobj1 += (float)(__bf16)g1;                  // (g1 / g2 are 0 where the chunk has no such column)
+            bobj2 += (float)(__bf16)g2;
         }
         *(uint4 *)(hg + pix * hg_cs + c8) = uint4{ow[0], ow[1], ow[2], ow[3]};
     };
     // (two or four pixels in flight per wave measured slower -- 122.8 / 129.2 us against 120.9 per launch: the occupancy they cost is
     // worth more than the extra loads in flight)
-    for (long long pix = wave0; pix < npix; pix += nwaves)
-        for (int chunk = lane; chunk < cpr; chunk += 64) one(pix, chunk * 8, *(const loss_bf16x8 *)(head + pix * head_cs + chunk * 8));
+    // this wave's pixels: every nwaves-th of all, or (FOLD) the stream of pixel lane wave0 % npl of slab wave0 / npl
+    if constexpr (FOLD) {        // (npix < 2^31, host check: 32-bit scalar counters)
+        const int w = (int)wave0, sl = w / npl;
+        const int pix_end = w < bias_rows ? (int)min(npix, ((long long)sl + 1) * slab) : 0;
+        for (int ip = sl * slab + (w - sl * npl); ip < pix_end; ip += npl) {
+            const long long pix = ip;
+            for (int chunk = lane; chunk < cpr; chunk += 64) one(pix, chunk * 8, *(const loss_bf16x8 *)(head + pix * head_cs + chunk * 8));
+        }
+    } else {
+        for (long long pix = wave0; pix < npix; pix += nwaves)
+            for (int chunk = lane; chunk < cpr; chunk += 64) one(pix, chunk * 8, *(const loss_bf16x8 *)(head + pix * head_cs + chunk * 8));
+    }
     __shared__ float wsum[4];
+    if constexpr (FOLD) {
+        // cpr <= 64 (host check): chunk == lane.  The wave's row: the objectness channels from their registers, the others from LDS
+        // (channels past C: lanes that never ran, zeros)
+        if (wave0 < bias_rows && lane * 8 < bias_cs) {
+            const int c8 = lane * 8, a0 = c8 / no, k0 = c8 - a0 * no;
+            int e1 = 5 - k0;
+            if (e1 < 0) e1 += no;
+            const int e2 = e1 + no;
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 8; e++) v[e] = e == e1 ? bobj1 : (e == e2 ? bobj2 : bred[threadIdx.x >> 6][brow + e]);
+            float4 *row = (float4 *)(bias_part + (size_t)wave0 * bias_cs + c8);
+            row[0] = make_float4(v[0], v[1], v[2], v[3]);
+            row[1] = make_float4(v[4], v[5], v[6], v[7]);
+        }
+        acc = wave_sum(acc);
+        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const float t = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+            if (t != 0.f) atomicAdd(items + 0, t * coef);
+        }
+        return;
+    }
     acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
     __syncthreads();
@@ -620,13 +692,43 @@ int ryolo_yolo_loss_nhwc(const void *head, int head_cstride, const float *p, int
                                     head_grad_cstride, items, stream_);
 }
 
+// workgroups of the 'default'-arc dense NHWC pass without the bias fold (with it: one wave per row of bias partial sums)
+static long long dense_nhwc_blocks(long long npix) {
+    const long long nb = (npix + 3) / 4;
+    return nb > 8192 ? 8192 : nb;
+}
+
+int ryolo_yolo_loss_bias_rows(int bs, int na, int ny, int nx, int no, int arc) {
+    if (bs <= 0 || na <= 0 || ny <= 0 || nx <= 0 || no < 6 || arc != 0) return 0;
+    const long long C = (long long)na * no, npix = (long long)bs * ny * nx;
+    if ((C & 7) || C > BIAS_FOLD_CMAX || npix >= 0x7fffffffll) return 0;
+    long long slab = 0;
+    int npl = 0;
+    const long long rows = (long long)ryolo_bn_act_bwd_bias_order(npix, (int)C, &slab, &npl) * npl;     // one row per (slab, pixel lane)
+    return rows > 0 && rows <= 0x3fffffff && slab < 0x7fffffff ? (int)rows : 0;
+}
+
 int ryolo_yolo_loss_nhwc_arc(const void *head, int head_cstride, const float *p, int bs, int na, int ny, int nx, int no, int nc,
                              const float *w, int NT, const long long *b, const long long *gj, const long long *gi,
                              const long long *cls, const float *txy, const float *twh, const float *ta, const float *anchor_vec,
                              const float *npos, float giou, float reg_w, float cls_w, float cls_pw, float obj_w, float obj_pw,
                              int iou_mode, int arc, float fl_gamma, unsigned *bitmap, float *dp_sparse, void *head_grad,
                              int head_grad_cstride, float *items, void *stream_) {
+    return ryolo_yolo_loss_nhwc_bias(head, head_cstride, p, bs, na, ny, nx, no, nc, w, NT, b, gj, gi, cls, txy, twh, ta, anchor_vec, npos,
+                                     giou, reg_w, cls_w, cls_pw, obj_w, obj_pw, iou_mode, arc, fl_gamma, bitmap, dp_sparse, head_grad,
+                                     head_grad_cstride, items, nullptr, 0, stream_);
+}
+
+int ryolo_yolo_loss_nhwc_bias(const void *head, int head_cstride, const float *p, int bs, int na, int ny, int nx, int no, int nc,
+                              const float *w, int NT, const long long *b, const long long *gj, const long long *gi,
+                              const long long *cls, const float *txy, const float *twh, const float *ta, const float *anchor_vec,
+                              const float *npos, float giou, float reg_w, float cls_w, float cls_pw, float obj_w, float obj_pw,
+                              int iou_mode, int arc, float fl_gamma, unsigned *bitmap, float *dp_sparse, void *head_grad,
+                              int head_grad_cstride, float *items, float *bias_part, int bias_cstride, void *stream_) {
     if (!arc_ok(arc, no, nc)) return RYOLO_EINVAL;
+    if (bias_part && (ryolo_yolo_loss_bias_rows(bs, na, ny, nx, no, arc) <= 0 || bias_cstride < na * no || bias_cstride > BIAS_FOLD_CMAX ||
+                      (bias_cstride & 7) || ((uintptr_t)bias_part & 15)))
+        return RYOLO_EINVAL;
     if (!head || !p || !w || !b || !gj || !gi || !cls || !txy || !twh || !ta || !anchor_vec || !npos || !bitmap || !dp_sparse ||
         !head_grad || !items)
         return RYOLO_EINVAL;
@@ -656,16 +758,30 @@ int ryolo_yolo_loss_nhwc_arc(const void *head, int head_cstride, const float *p,
         return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
     }
     if (npix >= 0x7fffffffll) return RYOLO_EINVAL;
-    nb = (npix + 3) / 4;
-    if (nb > 8192) nb = 8192;
+    nb = dense_nhwc_blocks(npix);
+    if (bias_part) {
+        long long slab = 0;
+        int npl = 0;
+        const long long rows = (long long)ryolo_bn_act_bwd_bias_order(npix, C, &slab, &npl) * npl;
+        nb = (rows + 3) / 4;                                 // a wave per (slab, pixel lane) stream of the separate bias pass
+        if (no == 7)
+            hipLaunchKernelGGL((yolo_loss_dense_nhwc_kernel<7, true>), dim3((unsigned)nb), dim3(256), 0, stream, (const __bf16 *)head,
+                               head_cstride, npix, ny * nx, na, no, coef, dp_sparse, bitmap, (__bf16 *)head_grad, head_grad_cstride,
+                               items, bias_part, bias_cstride, (int)rows, (int)slab, npl);
+        else
+            hipLaunchKernelGGL((yolo_loss_dense_nhwc_kernel<0, true>), dim3((unsigned)nb), dim3(256), 0, stream, (const __bf16 *)head,
+                               head_cstride, npix, ny * nx, na, no, coef, dp_sparse, bitmap, (__bf16 *)head_grad, head_grad_cstride,
+                               items, bias_part, bias_cstride, (int)rows, (int)slab, npl);
+        return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+    }
     if (no == 7)
-        hipLaunchKernelGGL(yolo_loss_dense_nhwc_kernel<7>, dim3((unsigned)nb), dim3(256), 0, stream, (const __bf16 *)head,
+        hipLaunchKernelGGL((yolo_loss_dense_nhwc_kernel<7, false>), dim3((unsigned)nb), dim3(256), 0, stream, (const __bf16 *)head,
                            head_cstride, npix, ny * nx, na, no, coef, dp_sparse, bitmap, (__bf16 *)head_grad, head_grad_cstride,
-                           items);
+                           items, (float *)nullptr, 0, 0, 1, 1);
     else
-        hipLaunchKernelGGL(yolo_loss_dense_nhwc_kernel<0>, dim3((unsigned)nb), dim3(256), 0, stream, (const __bf16 *)head,
+        hipLaunchKernelGGL((yolo_loss_dense_nhwc_kernel<0, false>), dim3((unsigned)nb), dim3(256), 0, stream, (const __bf16 *)head,
                            head_cstride, npix, ny * nx, na, no, coef, dp_sparse, bitmap, (__bf16 *)head_grad, head_grad_cstride,
-                           items);
+                           items, (float *)nullptr, 0, 0, 1, 1);
     return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
 }
 

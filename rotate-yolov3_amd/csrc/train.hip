@@ -293,6 +293,46 @@ bn_act_bwd_fold_kernel(const float *__restrict__ part, int nrows, int C, int per
     out[((size_t)g * 3 + 2) * C + c] = d;
 }
 
+// The head convs' bias gradient from rows the loss's dense pass wrote (csrc/loss.hip: row slab * npl + l = the per-channel sums of the
+// stored head gradient over the pixels of pixel lane l of slab `slab` -- the streams of bn_act_bwd_reduce_kernel's bias form, added in
+// its order).  Two steps that add what is left in the order of that kernel's block reduce and of bn_act_bwd_finalize_kernel, so dbias
+// receives the bits the separate pass over the head gradient would have given it:
+//   lanes    out[slab][c] = ((0 + row[slab*npl + 0][c]) + row[slab*npl + 1][c]) + ...           (the reduce kernel's sum over pixel lanes)
+//   finalize slab lane ry adds slabs ry, ry + 32, ... ascending, then the 32 lanes in order; dbias[c] += g[0] * that
+__global__ void __launch_bounds__(256)
+head_bias_lanes_kernel(const float *__restrict__ rows, int npl, int cs, int C, float *__restrict__ out) {
+    const int c = blockIdx.x * 256 + threadIdx.x, slab = blockIdx.y;
+    if (c >= C) return;
+    float v = 0.f;
+    for (int q = 0; q < npl; q++) v += rows[((size_t)slab * npl + q) * cs + c];
+    out[(size_t)slab * C + c] = v;
+}
+
+__global__ void __launch_bounds__(1024)
+head_bias_finalize_kernel(const float *__restrict__ part, int nslab, int C, const float *__restrict__ gsc, float *__restrict__ dbias) {
+    __shared__ float red[32][33];
+    const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
+    const int c = blockIdx.x * 32 + cx;
+    float a = 0.f;
+    if (c < C) {
+        for (int s0 = ry; s0 < nslab; s0 += 32 * 8) {
+            float va[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const int s = s0 + 32 * u;
+                va[u] = s < nslab ? part[(size_t)s * C + c] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; u++) a += va[u];
+        }
+    }
+    red[ry][cx] = a;
+    __syncthreads();
+    if (ry != 0 || c >= C) return;
+    for (int k = 1; k < 32; k++) a += red[k][cx];
+    dbias[c] += gsc[0] * a;
+}
+
 // backward pass 2: dz = scale_c * (g - s1/M - xhat * s2/M), g = dy * act'(u).  4096 blocks whose grid stride is a multiple of
 // the 8-channel chunks per pixel whenever that count is a power of two: a thread then keeps ONE chunk for its whole walk, its
 // per-channel constants live in registers (with k = scale*invstd*s2/M the result is scale*g - k*z + (k*mean - scale*s1/M)),
@@ -564,6 +604,40 @@ static int bn_act_bwd_impl(const void *z, int z_cstride, const void *dy, int dy_
         if (act == 0) RYOLO_BN_APP(0); else if (act == 1) RYOLO_BN_APP(1); else RYOLO_BN_APP(2);
     }
 #undef RYOLO_BN_APP
+    return ok_launch();
+}
+
+/* slabs and pixel lanes of the reduce pass's bias form (scale == NULL) for a [npix][C] gradient: pixel lane l of slab s adds pixels
+ * s * slab_pixels + l, + pixel_lanes, ... (below the slab's end) one after the other.  Returns the number of slabs (0: bad arguments). */
+int ryolo_bn_act_bwd_bias_order(long long npix, int C, long long *slab_pixels, int *pixel_lanes) {
+    if (npix <= 0 || C <= 0 || (C & 7) || !slab_pixels || !pixel_lanes) return 0;
+    int CT = 32;
+    while (CT > 1 && CT > C / 8) CT >>= 1;
+    const long long SL = bwd_slab(npix), nslab = (npix + SL - 1) / SL;
+    if (nslab > 0x7fffffffll) return 0;
+    *slab_pixels = SL;
+    *pixel_lanes = 256 / CT;
+    return (int)nslab;
+}
+
+size_t ryolo_head_bias_workspace_bytes(long long npix, int C) {
+    long long SL;
+    int npl;
+    const int nslab = ryolo_bn_act_bwd_bias_order(npix, C, &SL, &npl);
+    return (size_t)nslab * C * 4;
+}
+
+int ryolo_head_bias_finalize(const float *bias_part, long long npix, int bias_cstride, int C, const float *g, float *dbias, void *workspace,
+                             size_t workspace_bytes, void *stream_) {
+    long long SL;
+    int npl;
+    const int nslab = ryolo_bn_act_bwd_bias_order(npix, C, &SL, &npl);
+    if (!bias_part || !g || !dbias || nslab <= 0 || bias_cstride < C || !workspace || workspace_bytes < (size_t)nslab * C * 4 || nslab > 65535)
+        return RYOLO_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(head_bias_lanes_kernel, dim3((C + 255) / 256, nslab), dim3(256), 0, stream, bias_part, npl, bias_cstride, C,
+                       (float *)workspace);
+    hipLaunchKernelGGL(head_bias_finalize_kernel, dim3((C + 31) / 32), dim3(1024), 0, stream, (const float *)workspace, nslab, C, g, dbias);
     return ok_launch();
 }
 

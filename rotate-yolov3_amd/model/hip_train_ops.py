@@ -30,6 +30,7 @@ _lib.declare("ryolo_conv_wgrad_workspace_bytes", C.c_size_t, [_P])
 _lib.declare("ryolo_conv2d_wgrad", C.c_int, [_P, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp])
 _lib.declare("ryolo_conv2d_wgrad_partials", C.c_int, [_P, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp])
 _lib.declare("ryolo_conv2d_wgrad_reduce", C.c_int, [_P, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp])
+_lib.declare("ryolo_conv_head_decode_store", C.c_int, [_P, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp])
 _lib.declare("ryolo_upsample2x_bwd", C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp])
 _lib.declare("ryolo_pgrad_to_nhwc", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp])
 
@@ -47,6 +48,11 @@ _lib.declare("ryolo_yolo_loss_arc", C.c_int, [_vp] + [C.c_int] * 6 + [_vp, C.c_i
              [C.c_int, C.c_int, C.c_float] + [_vp] * 4)
 _lib.declare("ryolo_yolo_loss_nhwc_arc", C.c_int, [_vp, C.c_int, _vp] + [C.c_int] * 6 + [_vp, C.c_int] + [_vp] * 9 + [C.c_float] * 6 +
              [C.c_int, C.c_int, C.c_float] + [_vp, _vp, _vp, C.c_int, _vp, _vp])
+_lib.declare("ryolo_yolo_loss_bias_rows", C.c_int, [C.c_int] * 6)
+_lib.declare("ryolo_yolo_loss_nhwc_bias", C.c_int, [_vp, C.c_int, _vp] + [C.c_int] * 6 + [_vp, C.c_int] + [_vp] * 9 + [C.c_float] * 6 +
+             [C.c_int, C.c_int, C.c_float] + [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp])
+_lib.declare("ryolo_head_bias_workspace_bytes", C.c_size_t, [C.c_longlong, C.c_int])
+_lib.declare("ryolo_head_bias_finalize", C.c_int, [_vp, C.c_longlong, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp])
 ARC_FOCAL, ARC_UBCE, ARC_UCE = 1, 2, 4
 
 
@@ -262,6 +268,19 @@ def conv_fwd_plain(d, x, packed_w, ones, shift, z):
                                               None, z.data_ptr(), _s(x.device)), "ryolo_conv2d_bn_act")
 
 
+def conv_head_decode_store(hf, x, packed_w, ones, shift, head, p):
+    """A YOLO head of the training forward in one launch: head = conv(x, W) + shift (NHWC bf16, what conv_fwd_plain stores) and
+    p [bs, na, ny, nx, no] fp32, the raw rows ryolo_yolo_decode hands out.  hf: dict(desc, na, no) of plan.plan_train."""
+    d = ConvDesc(*hf['desc'])
+    d.in_cstride = _check_nhwc(x, "x")
+    hcs = _check_nhwc(head, "head")
+    if not p.is_contiguous() or p.dtype != torch.float32:
+        raise ValueError("conv_head_decode_store: p must be contiguous fp32")
+    _lib.check(_lib.lib().ryolo_conv_head_decode_store(C.byref(d), x.data_ptr(), packed_w.data_ptr(), ones.data_ptr(), shift.data_ptr(),
+                                                       hf['na'], hf['no'], head.data_ptr(), hcs, p.data_ptr(), _s(x.device)),
+               "ryolo_conv_head_decode_store")
+
+
 def bn_finalize(part, C_, count, gamma, beta, eps=1e-5, momentum=0.1, running_mean=None, running_var=None, out=None):
     dev = part.device
     if out is None:
@@ -418,23 +437,48 @@ def yolo_loss_head(p, hd, nc, h, bitmap, dp, items, arc=0):
                "ryolo_yolo_loss_arc")
 
 
-def yolo_loss_head_nhwc(head, p, hd, nc, h, bitmap, dp_sparse, head_g, items, arc=0):
+def yolo_loss_head_nhwc(head, p, hd, nc, h, bitmap, dp_sparse, head_g, items, arc=0, bias_part=None):
     """yolo_loss_head for a head of the training engine: `head` / `head_g` are the NHWC bf16 activation and gradient buffers of
-    the head conv, dp_sparse an all-zero fp32 scratch shaped like p (left all-zero); see ryolo_yolo_loss_nhwc."""
+    the head conv, dp_sparse an all-zero fp32 scratch shaped like p (left all-zero); see ryolo_yolo_loss_nhwc.
+    bias_part ([yolo_loss_bias_rows(p, arc), >= C] fp32, or None): the dense pass also writes rows of partial sums of the head
+    conv's bias gradient (head_bias_finalize turns them into dbias)."""
     bs, na, ny, nx, no = p.shape
     w = hd['w'].contiguous()
     n = hd['npos'] if 'npos' in hd else w.sum()
     c = lambda t: t.contiguous()   # noqa: E731
     b, gj, gi, cls = c(hd['b']), c(hd['gj']), c(hd['gi']), c(hd['cls'])
     txy, twh, ta, av = c(hd['gxy']), c(hd['gwh']), c(hd['ga']), c(hd['av'].float())
-    _lib.check(_lib.lib().ryolo_yolo_loss_nhwc_arc(head.data_ptr(), head.stride(2), p.data_ptr(), bs, na, ny, nx, no, nc, w.data_ptr(),
-                                                   w.shape[1], b.data_ptr(), gj.data_ptr(), gi.data_ptr(), cls.data_ptr(),
-                                                   txy.data_ptr(), twh.data_ptr(), ta.data_ptr(), av.data_ptr(), n.data_ptr(),
-                                                   float(h['giou']), float(h['reg']), float(h['cls']), float(h['cls_pw']),
-                                                   float(h['obj']), float(h['obj_pw']), 1 if h.get('riou', 0) else 0, int(arc),
-                                                   float(h.get('fl_gamma', 0.0)), bitmap.data_ptr(), dp_sparse.data_ptr(),
-                                                   head_g.data_ptr(), head_g.stride(2), items.data_ptr(), _s(p.device)),
-               "ryolo_yolo_loss_nhwc_arc")
+    if bias_part is not None and (bias_part.dtype != torch.float32 or not bias_part.is_contiguous()
+                                  or bias_part.shape[0] != yolo_loss_bias_rows(p, arc)):
+        raise ValueError("yolo_loss_head_nhwc: bias_part must be contiguous fp32 [yolo_loss_bias_rows, >= C]")
+    _lib.check(_lib.lib().ryolo_yolo_loss_nhwc_bias(head.data_ptr(), head.stride(2), p.data_ptr(), bs, na, ny, nx, no, nc, w.data_ptr(),
+                                                    w.shape[1], b.data_ptr(), gj.data_ptr(), gi.data_ptr(), cls.data_ptr(),
+                                                    txy.data_ptr(), twh.data_ptr(), ta.data_ptr(), av.data_ptr(), n.data_ptr(),
+                                                    float(h['giou']), float(h['reg']), float(h['cls']), float(h['cls_pw']),
+                                                    float(h['obj']), float(h['obj_pw']), 1 if h.get('riou', 0) else 0, int(arc),
+                                                    float(h.get('fl_gamma', 0.0)), bitmap.data_ptr(), dp_sparse.data_ptr(),
+                                                    head_g.data_ptr(), head_g.stride(2), items.data_ptr(),
+                                                    bias_part.data_ptr() if bias_part is not None else None,
+                                                    bias_part.shape[1] if bias_part is not None else 0, _s(p.device)),
+               "ryolo_yolo_loss_nhwc_bias")
+
+
+def yolo_loss_bias_rows(p, arc=0):
+    """rows of bias partial sums the dense pass of yolo_loss_head_nhwc writes for head p [bs, na, ny, nx, no]; 0: fold not served"""
+    bs, na, ny, nx, no = p.shape
+    return _lib.lib().ryolo_yolo_loss_bias_rows(bs, na, ny, nx, no, int(arc))
+
+
+def head_bias_ws_bytes(npix, c):
+    return _lib.lib().ryolo_head_bias_workspace_bytes(npix, c)
+
+
+def head_bias_finalize(bias_part, npix, c, g, dbias, ws):
+    """dbias[:c] += g[0] * sum over the rows of bias_part, in the order bn_act_bwd's bias form sums the [npix, c] head gradient (for
+    g == 1: the same bits)"""
+    _lib.check(_lib.lib().ryolo_head_bias_finalize(bias_part.data_ptr(), npix, bias_part.shape[1], c, g.data_ptr(),
+                                                   dbias.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _s(dbias.device)),
+               "ryolo_head_bias_finalize")
 
 
 def scale_bf16_if(g, buf):

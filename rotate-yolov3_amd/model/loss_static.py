@@ -185,6 +185,9 @@ class _FusedLossFn(torch.autograd.Function):
             g1 = g.detach().reshape(1).float()
             for hg in heads:
                 tr.scale_bf16_if(g1, hg)
+            # the head bias gradients folded into the dense pass are sums of the UNSCALED values: the engine's finalize multiplies
+            # them by this scalar (a stable address: the backward segments replay as graphs)
+            ctx.state['eng'].head_gscale.copy_(g1)
         else:
             for buf in pg:
                 buf.mul_(g)
@@ -273,6 +276,7 @@ class FusedLoss(object):
         self._last_state = st
         if st.get('head_g') is not None:
             eng.head_g_ready = True        # (python side effect: must not live in the captured body)
+            eng.head_bias_ready = st.get('bias_parts')     # ... and so are the rows of the heads' bias gradients (per head, or None)
         loss = _FusedLossFn.apply(self, *p)
         return loss, torch.cat((st['items'][:3], loss.detach()))
 
@@ -322,11 +326,15 @@ class FusedLoss(object):
             arc = tr.arc_flags(core.arc)
             if 'bitmaps' not in st:
                 st['bitmaps'] = [tr.yolo_loss_bitmap(q, core.nc, arc) for q in st['leaves']]
+            if 'bias_parts' not in st:     # (first call, eager: the engine's scratch exists before any capture)
+                st['bias_parts'] = st['eng'].head_bias_parts(arc) if st.get('head_g') is not None else None
+            parts = st['bias_parts']
             st['items'].zero_()
             for k, (q, hd, bm, dp) in enumerate(zip(st['leaves'], heads, st['bitmaps'], st['pg'])):
                 bm.zero_()
                 if st.get('head_g') is not None:
-                    tr.yolo_loss_head_nhwc(st['head'][k], q.detach(), hd, core.nc, h, bm, dp, st['head_g'][k], st['items'], arc)
+                    tr.yolo_loss_head_nhwc(st['head'][k], q.detach(), hd, core.nc, h, bm, dp, st['head_g'][k], st['items'], arc,
+                                           bias_part=parts[k] if parts is not None else None)
                 else:
                     tr.yolo_loss_head(q.detach(), hd, core.nc, h, bm, dp, st['items'], arc)
 

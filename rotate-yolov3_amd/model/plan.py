@@ -313,12 +313,16 @@ def plan_eval(defs, convs, yolos, N, H, W, stem_pair=True, head_decode=True, cin
 
 
 # ------------------------------------------------------------------------------------------------ training
-def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, cin=3):
+def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, cin=3, yolos=None, head_decode=True):
     """TrainPlan(shapes, buffers, x, act, grd, forward, blocks, backward).  act[i] / grd[i]: activation / gradient view per layer
     (same concat / slice structure).  forward: (kind, layer, record) with kind =
       conv   a block: layer, desc, xin, xin_g (None for layer 0), y, dy, res, res_g, res_alias (the skip source's gradient IS dy),
              bn, act, shape (C, H, W of the conv output z), recompute / one_pass (layer 0 without stored z / dz); with BatchNorm
-             z and dz are buffers of their own (unless recompute / one_pass), without they are y and dy
+             z and dz are buffers of their own (unless recompute / one_pass), without they are y and dy;
+             head_fused: None, or dict(desc, na, no) for a YOLO head whose conv, p rows and head-tensor store run as one launch
+             (ryolo_conv_head_decode_store) -- the conditions of plan_eval's fused head: alone on its input, no BatchNorm, k1 s1, the
+             library's own ryolo_conv_head_decode_supported (needs `yolos[i]` = (na, no); whether the block is linear is the engine's
+             half: training reads the activation from the modules)
       add    (a, b, y, a_g, b_g, dy)        up  (x, y, x_g, dy)        yolo  (head, head_g)
     blocks: the conv records.  backward: (kind, layer, flags) in launch order (forward reversed); flags say which gradient views the
     entry is the FIRST to write (it overwrites, later ones accumulate): conv (res_g, xin_g), add (a_g, b_g), up x_g; yolo: head index."""
@@ -393,9 +397,16 @@ def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, 
             # passes instead of being stored and re-read (include/ryolo.h: ryolo_conv0_*); its one-pass backward never materialises dz
             recompute = bool(i == 0 and cv['bn'] and i not in conv_res and conv0_recompute
                              and _query('ryolo_conv0_recompute_supported', desc))
+            head_fused = None
+            if (head_decode and yolos is not None and i + 1 < n and defs[i + 1]['type'] == 'yolo' and readers[i] == [i + 1] and i not in home
+                    and i not in conv_res and not cv['bn'] and cv['k'] == 1 and cv['s'] == 1 and c % 8 == 0):
+                na, no = yolos[i + 1]
+                ht = (N, xin.H, xin.W, xin.C, c, 1, 1, 0, xin.cs, c, 0, ACT_LINEAR, 0.0, 1, 0)
+                if _query('ryolo_conv_head_decode_supported', ht, int(na), int(no)):
+                    head_fused = dict(desc=ht, na=int(na), no=int(no))
             blk = dict(layer=i, desc=desc, xin=xin, xin_g=xin_g, y=y, dy=dy, res=act[conv_res[i]] if i in conv_res else None,
                        res_g=grd[conv_res[i]] if i in conv_res else None, res_alias=res_alias, bn=cv['bn'], act=cv['act'], shape=shp[i],
-                       recompute=recompute, one_pass=bool(recompute and xin_g is None and conv0_one_pass))
+                       recompute=recompute, one_pass=bool(recompute and xin_g is None and conv0_one_pass), head_fused=head_fused)
             blocks.append(blk)
             forward.append(('conv', i, blk))
         elif t == 'shortcut':

@@ -72,9 +72,12 @@ class TrainEngine(object):
         # ---- the plan (model/plan.py): shapes, activation / gradient buffers (same concat / slice structure), blocks, who writes first.
         # RYOLO_CONV0_RECOMPUTE=0 stores layer 0's conv output like any other, RYOLO_CONV0_ONE_PASS=0 keeps its dz and weight gradient
         convs = {i: self._conv_attrs(mods[i]) for i, d in enumerate(defs) if d['type'] == 'convolutional'}
+        # RYOLO_HEAD_DECODE=0 (the inference engine's switch) keeps a YOLO head's conv and its decode as two launches here too
         tp = self._tplan = plan.plan_train(defs, convs, self.bs, self.H, self.W,
                                            conv0_recompute=os.environ.get('RYOLO_CONV0_RECOMPUTE', '1') != '0',
-                                           conv0_one_pass=os.environ.get('RYOLO_CONV0_ONE_PASS', '1') != '0', cin=cin)
+                                           conv0_one_pass=os.environ.get('RYOLO_CONV0_ONE_PASS', '1') != '0', cin=cin,
+                                           yolos={i: (mods[i].na, model.nc + 6) for i, d in enumerate(defs) if d['type'] == 'yolo'},
+                                           head_decode=os.environ.get('RYOLO_HEAD_DECODE', '1') != '0')
         self.shp = tp.shapes
 
         def new_buf(c, h, w):
@@ -118,6 +121,9 @@ class TrainEngine(object):
                            xin=xin, xin_g=tv(rec['xin_g']), z=z, dz=dz, y=y, dy=dy, desc=desc, res=tv(rec['res']), res_g=tv(rec['res_g']),
                            res_alias=rec['res_alias'], cin_k=xin.shape[-1], k=desc.ksize, s=desc.stride, pad=desc.pad,
                            npix=self.bs * h * w, C=c, recompute=rec['recompute'])
+                # a linear head conv the plan marked: conv + p rows + head-tensor store in one launch, issued at the yolo entry
+                if rec.get('head_fused') and not actmod and not blk['mish']:
+                    blk['head_fused'] = rec['head_fused']
                 wgrad_ws = max(wgrad_ws, tr.wgrad_ws_bytes(desc))
                 bn_ws = max(bn_ws, tr.bn_bwd_ws_bytes(blk['npix'], c))
                 self.blocks.append(blk)
@@ -135,11 +141,33 @@ class TrainEngine(object):
                 if model.nc + 6 > 96 or m.na * (model.nc + 6) > 1024:
                     io = torch.empty((self.bs, m.na * h * w, model.nc + 6), dtype=torch.float32, device=device)
                 self.p.append(pbuf)
-                fwd.append(('yolo', i, (tv(rec[0]), tv(rec[1]), m, anchors, pbuf, io, h, w)))
+                hb = self.blocks[-1] if self.blocks and self.blocks[-1]['i'] == i - 1 and self.blocks[-1].get('head_fused') else None
+                if hb is not None and (hb['head_fused']['na'], hb['head_fused']['no']) != (m.na, model.nc + 6):
+                    hb.pop('head_fused')
+                    hb = None
+                fwd.append(('yolo', i, (tv(rec[0]), tv(rec[1]), m, anchors, pbuf, io, h, w, hb)))
         # (head activation, head gradient) NHWC bf16 pairs in the order of self.p: the fused loss writes the gradients directly
         self.head_pairs = [(pl[0], pl[1]) for kind, _, pl in fwd if kind == 'yolo']
         self.fused_nhwc = False
         self.head_g_ready = False
+        # The head convs' bias gradients out of the fused loss's dense pass (csrc/loss.hip: rows of sums of the head gradient it stores,
+        # added in the order of the pass they replace, so the gradients keep their bits): the backward then only
+        # finalises the rows instead of re-reading the whole head gradient (bn_act_bwd's bias form).  Only for a head whose gradient the
+        # NHWC loss kernel wrote (head_g_ready) and whose conv output feeds the yolo layer alone; RYOLO_HEAD_BIAS_FOLD=0: the separate
+        # pass everywhere.
+        self.head_bias_fold = os.environ.get('RYOLO_HEAD_BIAS_FOLD', '1') != '0'
+        self.head_gscale = torch.ones(1, device=device)     # upstream gradient of the loss (written by the fused loss's backward)
+        self.head_bias_ready = None      # per head: the rows the latest fused loss call wrote (None: none)
+        self._bias_parts = self._bias_ws = None
+        self._fold_now = (False,) * len(self.head_pairs)    # per head: this backward takes the bias gradient from the rows
+        self._g_bwd_fold = None          # ... and what the captured backward graphs took
+        readers = plan._readers(defs)
+        for k, (hd, _) in enumerate(self.head_pairs):
+            for b in self.blocks:
+                i = b['i']
+                if (b['y'] is hd and b['bn'] is None and b['conv'].bias is not None and i + 1 < len(defs) and defs[i + 1]['type'] == 'yolo'
+                        and readers[i] == [i + 1]):
+                    b['head_k'] = k
         # (weight gradients on a second stream -- a parallel branch of the backward graphs -- were measured in rounds 2 and 5 and lost both
         #  times: 63.2 vs 62.6 ms, 50.07 vs 49.57 ms; wgrad_wide's two workgroups per CU fill the register file, nothing co-resides with it.
         #  The switch and its code were removed in round 6; profiles/r05_ab_log.txt keeps the numbers.)
@@ -267,6 +295,24 @@ class TrainEngine(object):
             if hooks:
                 for hk in list(hooks.values()):
                     hk(p)
+
+    def head_bias_parts(self, arc=0):
+        """Per head the [rows, cpad] fp32 scratch the fused loss's dense pass writes its bias-gradient rows to (None where the fold is
+        not served: another arc, more than 512 channels, a head conv without bias or with other readers), or None when the fold is
+        switched off.  Allocated once per engine: the loss and the backward graphs hold these addresses."""
+        if not self.head_bias_fold or arc != 0:
+            return None
+        if self._bias_parts is None:
+            by_head = {b['head_k']: b for b in self.blocks if 'head_k' in b}
+            parts, ws = [], 256
+            for k, q in enumerate(self.p):
+                rows = tr.yolo_loss_bias_rows(q, arc) if k in by_head else 0
+                parts.append(torch.empty((rows, ops.cpad(by_head[k]['C'])), dtype=torch.float32, device=self.device) if rows > 0 else None)
+                if rows > 0:
+                    ws = max(ws, tr.head_bias_ws_bytes(by_head[k]['npix'], by_head[k]['C']))
+            self._bias_parts = parts
+            self._bias_ws = torch.empty(ws, dtype=torch.uint8, device=self.device)
+        return self._bias_parts if any(q is not None for q in self._bias_parts) else None
 
     @staticmethod
     def _has_wgrad(b):
@@ -432,7 +478,9 @@ class TrainEngine(object):
                         bias = b['bias_pad']
                     else:
                         bias = self.zeros
-                    tr.conv_fwd_plain(b['desc'], b['xin'], b['packed'], self.ones, bias, b['z'])
+                    b['bias_now'] = bias
+                    if not b.get('head_fused'):            # (a fused head runs at its yolo entry, the next one)
+                        tr.conv_fwd_plain(b['desc'], b['xin'], b['packed'], self.ones, bias, b['z'])
                     b['stats'] = None
             elif kind == 'add':
                 a, bb, y = pl[0], pl[1], pl[2]
@@ -445,11 +493,16 @@ class TrainEngine(object):
                 _lib.check(L.ryolo_upsample_nhwc(xin.data_ptr(), xin.stride(2), y.data_ptr(), y.stride(2), nn_, hh, ww, cc, 2,
                                                  _lib.stream_ptr(dev)), "ryolo_upsample_nhwc")
             elif kind == 'yolo':
-                head, _, m, anchors, pbuf, io, hh, ww = pl
+                head, _, m, anchors, pbuf, io, hh, ww, hb = pl
                 stride = float(max(self.H, self.W)) / float(max(hh, ww))
-                _lib.check(L.ryolo_yolo_decode(head.data_ptr(), head.stride(2), self.bs, hh, ww, m.na, self.model.nc + 6,
-                                               anchors.data_ptr(), stride, 1.0, 0, io.data_ptr() if io is not None else None, m.na * hh * ww, 0,
-                                               pbuf.data_ptr(), _lib.stream_ptr(dev)), "ryolo_yolo_decode")
+                if hb is not None:
+                    # the head conv, the raw p rows and the head tensor's store as one launch (csrc/conv_pw.hip MODE 5): the head is
+                    # not written by one kernel and re-read by the next
+                    tr.conv_head_decode_store(hb['head_fused'], hb['xin'], hb['packed'], self.ones, hb['bias_now'], head, pbuf)
+                else:
+                    _lib.check(L.ryolo_yolo_decode(head.data_ptr(), head.stride(2), self.bs, hh, ww, m.na, self.model.nc + 6,
+                                                   anchors.data_ptr(), stride, 1.0, 0, io.data_ptr() if io is not None else None, m.na * hh * ww, 0,
+                                                   pbuf.data_ptr(), _lib.stream_ptr(dev)), "ryolo_yolo_decode")
                 # what YOLOLayer.forward would have set (model_utils.py:16-35): the loss reads ng / anchor_vec
                 if (m.nx, m.ny) != (ww, hh):
                     from .models import create_grids
@@ -461,10 +514,12 @@ class TrainEngine(object):
         with torch.cuda.device(dev), torch.no_grad():
             if not hasattr(self, "static_pg"):
                 self.static_pg = [torch.zeros_like(p) for p in self.p]
-            ready = self.head_g_ready
-            self.head_g_ready = False
+            ready, bias_ready = self.head_g_ready, self.head_bias_ready
+            self.head_g_ready, self.head_bias_ready = False, None
+            fold = [False] * len(self.static_pg)
             for k, (buf, g) in enumerate(zip(self.static_pg, pgrads)):
                 if g is not None and ready and g.data_ptr() == buf.data_ptr():
+                    fold[k] = bias_ready is not None and bias_ready[k] is not None     # ... and the rows of its bias gradient
                     continue                                  # the NHWC loss kernel already wrote this head's gradient
                 if g is None:
                     buf.zero_()
@@ -480,8 +535,17 @@ class TrainEngine(object):
                 self._ensure_reduce_batches(segs)
             if self.g_bwd is None:
                 self.g_bwd = [None] * len(segs)
+                self._g_bwd_fold = None
+            self._fold_now = tuple(fold)
+            eager = not self.use_graph or self.steps < 2 or self.force_eager
+            if not eager:
+                # the graphs hold ONE source of the head bias gradients (the loss's rows or the pass over the head gradient); a step whose
+                # head gradients arrive the other way (e.g. the eager loss mirror after fused steps) launches eagerly
+                if self._g_bwd_fold is None:
+                    self._g_bwd_fold = self._fold_now
+                eager = self._g_bwd_fold != self._fold_now
             for k, (lo, hi, params) in enumerate(segs):
-                if not self.use_graph or self.steps < 2 or self.force_eager:
+                if eager:
                     self._backward_launch(lo, hi)
                 else:
                     if self.g_bwd[k] is None:
@@ -533,7 +597,12 @@ class TrainEngine(object):
                         tr.bn_act_bwd(b['z'], dy, b['stats'], b['actcode'], b['slope'], b['dz'],
                                       self._grad_of(bn.weight), self._grad_of(bn.bias), dsl, self.ws_b)
                 elif conv.bias is not None:
-                    tr.bn_act_bwd(b['z'], dy, None, 0, None, None, None, self._grad_of(conv.bias), None, self.ws_b)
+                    hk = b.get('head_k')
+                    if hk is not None and self._fold_now[hk]:
+                        # the loss's dense pass summed the head gradient while storing it: finalise its rows (x the upstream gradient)
+                        tr.head_bias_finalize(self._bias_parts[hk], b['npix'], b['C'], self.head_gscale, self._grad_of(conv.bias), self._bias_ws)
+                    else:
+                        tr.bn_act_bwd(b['z'], dy, None, 0, None, None, None, self._grad_of(conv.bias), None, self.ws_b)
                 if self.batch_reduce:
                     # partial tiles only, into the layer's own workspace; the segment's reduces run as one launch below
                     tr.conv_wgrad_partials(b['desc'], b['xin'], b['dz'], conv.in_channels, self._grad_of(conv.weight), True, b['ws_w'])

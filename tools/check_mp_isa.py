@@ -185,7 +185,7 @@ def check_conv_pw(d):
     the generated code: the prologue issues (RING-1) x LPU fills and THEN WD x WL filter loads; iteration kt of the first row block
     issues [NREQ requests (kt == 0)] [LPU fills] [WL filter loads while kt + WD < KT] in that order; the wait in front of its barrier
     is the number the model computes (clamped to 63); no vmcnt(0) and no scratch operation sits between the first and the last MFMA
-    (MODE 4 excepted: its decode stage drains once per row block by design)."""
+    (MODES 4 and 5 excepted: their decode / head-store stage drains once per row block by design)."""
     src = os.path.join(ROOT, "rotate-yolov3_amd", "csrc", "conv_pw.hip")
     sfile = os.path.join(d, "conv_pw-hip-amdgcn-amd-amdhsa-gfx950.s")
     if not os.path.exists(sfile):
@@ -207,7 +207,7 @@ def check_conv_pw(d):
         i = j
         found += 1
         LPU, WL, WD = (PF * 16 // 8) // NW, 2 * CF, min(3, KT)
-        nstg = 0 if MODE == 4 else (PF if CF == 2 else PF // 2)
+        nstg = 0 if MODE in (4, 5) else (PF if CF == 2 else PF // 2)
         NREQ = (nstg if MODE in (2, 3) else 0) + (nstg if MODE == 3 else 0)
         toks = []               # (kind, value): F fill, L other buffer load, S store, w wait, B barrier, m mfma
         for l in body:
@@ -249,7 +249,7 @@ def check_conv_pw(d):
                 errs.append("first row block, iteration %d waits vmcnt(%s) in front of its barrier, the model says %d" % (kt, waits[-1] if waits else None, model))
         last_m = max(k for k, t in enumerate(toks) if t[0] == "m")
         span = toks[first_m:last_m + 1]
-        if MODE != 4 and any(t == ("w", 0) for t in span):
+        if MODE not in (4, 5) and any(t == ("w", 0) for t in span):
             errs.append("vmcnt(0) between the MFMAs")
         if any(t[0] == "X" for t in span if True) and MODE != 3:
             errs.append("scratch operation between the MFMAs")

@@ -131,6 +131,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--ab", action="append", default=[], help="name=VAR:VALUE[,VAR:VALUE...]; replaces the built-in pair of settings")
+    ap.add_argument("--alternate", action="store_true", help="reverse the settings' order in odd rounds and print the per-round pairs")
     ap.add_argument("--forward", action="store_true", help="also the bs-32 eval forward under each setting")
     ap.add_argument("--forward-only", action="store_true", help="skip the training step")
     a = ap.parse_args()
@@ -144,14 +145,26 @@ def main():
         return
     steps = {name: make(a, dev, name) for name in SETTINGS}
     times = {name: [] for name in SETTINGS}
-    for _ in range(a.rounds):
-        for name, st in steps.items():
+    for r in range(a.rounds):
+        order = list(steps.items())
+        if a.alternate and r % 2:
+            order.reverse()                  # both orders: whoever runs second in a round inherits the first one's cache and clock state
+        for name, st in order:
             torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
             for _ in range(a.steps):
                 st()
             torch.cuda.synchronize(dev)
             times[name].append((time.perf_counter() - t0) / a.steps * 1e3)
+    if a.alternate:                          # the rounds as measured (round r of every setting ran back to back): the A/B pairs
+        names = list(times)
+        print("round  " + "  ".join("%12s" % n[:12] for n in names) + "   (ms per step; odd rounds ran in reverse order)")
+        for r in range(a.rounds):
+            print("%5d  " % r + "  ".join("%12.3f" % times[n][r] for n in names))
+        for n in names[1:]:
+            d = [times[n][r] - times[names[0]][r] for r in range(a.rounds)]
+            print("%s - %s: mean %+.3f ms, per round %s, spread (max - min) %.3f ms" % (
+                n, names[0], sum(d) / len(d), " ".join("%+.3f" % q for q in d), max(d) - min(d)))
     for name, v in times.items():
         v = sorted(v)
         print("%-24s median %.2f ms  min %.2f ms  (%s)" % (name, v[len(v) // 2], v[0], " ".join("%.2f" % q for q in v)))

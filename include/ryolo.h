@@ -196,7 +196,7 @@ int ryolo_conv2d_bn_act_pair(const ryolo_conv_desc *first, const ryolo_conv_desc
                              const float *scale_first, const float *shift_first, const void *w_second, const float *scale_second,
                              const float *shift_second, int shortcut_from_input, void *y, void *stream);
 /* Which kernel ryolo_conv2d_bn_act (with_statistics: ryolo_conv2d_bn_act_stats) would launch for this descriptor on the current
- * device -- a dry run of the dispatch, nothing is enqueued.  For benchmarks and profiles (the per-kernel tables name the kernel
+ * device -- the plan the launch would execute, nothing is enqueued.  For benchmarks and profiles (the per-kernel tables name the kernel
  * that actually ran); -1 for an invalid descriptor. */
 #define RYOLO_CONV_KERNEL_MP256 1   /* conv_mp.hip, 256 pixels x 256 channels, one 8-wave workgroup per CU */
 #define RYOLO_CONV_KERNEL_MP192 2   /* conv_mp.hip, 192 x 256 */
@@ -211,7 +211,7 @@ int ryolo_conv2d_bn_act_pair(const ryolo_conv_desc *first, const ryolo_conv_desc
 #define RYOLO_CONV_KERNEL_MQ64 10   /* conv_mq.hip, 64 pixels x 128 channels: short tile lists (1x1 layers at 19^2 / 38^2) */
 #define RYOLO_CONV_KERNEL_IGEMM 16  /* + tile code of conv.hip's 128x128 / 256x64 / 256x32 ... tiles */
 int ryolo_conv_kernel_choice(const ryolo_conv_desc *desc, int with_residual, int with_statistics);
-/* The same dry run for the data gradient of `forward_desc` (ryolo_conv2d_dgrad; stride 2: the choice of the last parity class)
+/* The same query for the data gradient of `forward_desc` (ryolo_conv2d_dgrad; stride 2: the choice of the last parity class)
  * and for its weight gradient (ryolo_conv2d_wgrad): 32 / 64 / 128 = the square two-stage tile, 256 / 257 / 258 / 259 / 260 = the
  * three-stage tile 256x128 / 128x256 / 128x(3 taps x 64) / 128x128 / 64x128 (c_out x c_in), RYOLO_WGRAD_KERNEL_TAPS + v = the stem's per-tap kernels.
  * bench.py names the kernels of its in-run train-step table through them. */

@@ -23,10 +23,6 @@
 //     (optionally replicated 2x2 for the fused nearest upsample).
 //   - Workgroup -> tile map is XCD-aware: the 8 XCDs get contiguous chunks of the tile list, channel tiles
 //     fastest, so the blocks that share an activation tile run on one XCD's L2 back to back.
-#include <cstring>
-
-#include <mutex>
-
 #include "conv_common.h"
 
 using namespace ryolo_detail;
@@ -1284,51 +1280,42 @@ __global__ void nhwc_bf16_to_nchw_f32_kernel(const __bf16 *__restrict__ x, int N
     }
 }
 
-// tile code of a (BM, BN, WGM, WGN, NSTAGE) instantiation as ryolo_conv_desc::tile / RYOLO_CONV_KERNEL_IGEMM + code name it
-template <int BM, int BN, int WGM, int WGN, int NSTAGE>
-constexpr int igemm_tile_code() {
-    return BM == 256 ? (BN == 64 ? 2 : (BN == 32 ? 3 : 4)) : (WGM == 4 ? 6 : (WGN == 2 ? 7 : 1));
+// the persistent kernel exists for the two-stage tiles whose epilogue staging fits beside one stage of operands
+constexpr bool igemm_persist_tile(const IgemmTile &t) { return t.NSTAGE == 2 && t.BM * t.BN * 2 <= (t.BM + t.BN) * BK * 2; }
+// the instantiations with the folded BatchNorm reduce -- one tile per workgroup: the tiles the stride-1 data gradients of the 3x3 layers
+// with C_in <= 128 (128 x 128, 8 waves) and of the narrow layers (256 x 64, 256 x 32) take; persistent: the 1x1 128 x 128 2x2-wave tile
+constexpr bool igemm_reduce_tile(int ks, const IgemmTile &t, bool persist) {
+    return persist ? ks == 1 && t.code == 7 : (t.code == 1 && ks == 3) || t.code == 2 || t.code == 3;
 }
 
-// the one-tile-per-workgroup instantiations that exist with the folded BatchNorm reduce (bnreduce_plan mode 3): the tiles the stride-1
-// data gradients of the 3x3 layers with C_in <= 128 and of the narrow 1x1 layers take
-template <int KS, int BM, int BN, int WGM, int WGN, int NSTAGE>
-constexpr bool igemm_bnred_inst() {
-    return NSTAGE == 2 && ((BM == 128 && BN == 128 && WGM == 2 && WGN == 4 && KS == 3) || (BM == 256 && WGM == 4 && WGN == 1 && (BN == 64 || BN == 32)));
-}
-
-template <int KS, int BM, int BN, int WGM, int WGN, int NSTAGE, bool FAST, bool GEN>
-int launch_variant_impl(ConvParams &p, const ConvLaunch &lc) {
-    constexpr size_t smem = NSTAGE * (BM + BN) * BK * 2;
-    constexpr int code = RYOLO_CONV_KERNEL_IGEMM + igemm_tile_code<BM, BN, WGM, WGN, NSTAGE>();
-    p.nt = (p.Cout + BN - 1) / BN;
-    const dim3 grid((unsigned)((p.M + BM - 1) / BM * p.nt)), block(WGM * WGN * 64);
+// The launches of tile T = IGEMM_TILES[I].  One tile per workgroup: FAST / general addressing x GEN (statistics, strided output
+// placement), and the folded BatchNorm reduce where igemm_reduce_tile() has it.
+template <int KS, int I, bool FAST, bool GEN>
+int launch_one_tile(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc) {
+    constexpr IgemmTile T = IGEMM_TILES[I];
+    constexpr size_t smem = T.NSTAGE * (T.BM + T.BN) * BK * 2;
+    const dim3 grid((unsigned)pl.grid), block(T.WGM * T.WGN * 64);
     if (lc.bnred) {
-        if constexpr (FAST && !GEN && igemm_bnred_inst<KS, BM, BN, WGM, WGN, NSTAGE>()) {
-            if (lc.bnred_mode != 3 || p.stat_part || p.ups != 1 || p.os != 1) return RYOLO_EINVAL;
-            RYOLO_CONV_DRY_RUN(lc, code);
-            return launch_kernel<conv_igemm_kernel<KS, BM, BN, WGM, WGN, NSTAGE, true, false, true>>(grid, block, smem, lc.stream, p, *lc.bnred);
-        } else {
+        if constexpr (FAST && !GEN && igemm_reduce_tile(KS, T, false))
+            return launch_kernel<conv_igemm_kernel<KS, T.BM, T.BN, T.WGM, T.WGN, T.NSTAGE, true, false, true>>(grid, block, smem, lc.stream, p, *lc.bnred);
+        else
             return RYOLO_EINVAL;
-        }
     }
-    RYOLO_CONV_DRY_RUN(lc, code);
-    return launch_kernel<conv_igemm_kernel<KS, BM, BN, WGM, WGN, NSTAGE, FAST, GEN>>(grid, block, smem, lc.stream, p, BnRed());
+    return launch_kernel<conv_igemm_kernel<KS, T.BM, T.BN, T.WGM, T.WGN, T.NSTAGE, FAST, GEN>>(grid, block, smem, lc.stream, p, BnRed());
 }
-
-inline unsigned magic_u32(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 
 // the persistent kernel's instantiations: plain for every tile; with statistics for the 4-wave tiles (1x1 layers, short-K 3x3 layers);
-// with the folded BatchNorm reduce (bnreduce_plan mode 2) for the 1x1 128 x 128 2x2 tile.  Anything else is EINVAL, dry run or not.
-template <int KS, int BM, int BN, int WGM, int WGN>
-int launch_persist(ConvParams &p, int grid, const ConvLaunch &lc) {
+// with the folded BatchNorm reduce for the 1x1 128 x 128 2x2 tile
+template <int KS, int I>
+int launch_persist(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc) {
+    constexpr IgemmTile T = IGEMM_TILES[I];
+    constexpr int BM = T.BM, BN = T.BN, WGM = T.WGM, WGN = T.WGN;
     constexpr size_t smem = 2 * (BM + BN) * BK * 2;
-    constexpr int code = RYOLO_CONV_KERNEL_IGEMM + igemm_tile_code<BM, BN, WGM, WGN, 2>();
-    const dim3 g((unsigned)grid), b(WGM * WGN * 64);
+    const dim3 g((unsigned)pl.grid), b(WGM * WGN * 64);
+    p.ntiles = (int)(((long long)p.M + BM - 1) / BM * p.nt);
+    p.magic_nt = magic_u32(p.nt);
     if (lc.bnred) {
-        if constexpr (KS == 1 && BM == 128 && BN == 128 && WGM == 2 && WGN == 2) {
-            if (p.stat_part || p.ups != 1 || lc.bnred_mode != 2) return RYOLO_EINVAL;
-            RYOLO_CONV_DRY_RUN(lc, code);
+        if constexpr (igemm_reduce_tile(KS, T, true)) {
             constexpr size_t smem_bn = smem + (size_t)WGM * WGN * (BN / 8) * 24 * 4;
             return launch_kernel<conv_igemm_persist_kernel<KS, BM, BN, WGM, WGN, false, true>>(g, b, smem_bn, lc.stream, p, *lc.bnred);
         } else {
@@ -1337,82 +1324,72 @@ int launch_persist(ConvParams &p, int grid, const ConvLaunch &lc) {
     }
     if constexpr (WGM * WGN == 4) {
         if (p.stat_part) {
-            RYOLO_CONV_DRY_RUN(lc, code);
             constexpr size_t smem_st = smem + (size_t)WGM * 2 * BN * 4;
             return launch_kernel<conv_igemm_persist_kernel<KS, BM, BN, WGM, WGN, true>>(g, b, smem_st, lc.stream, p, BnRed());
         }
     }
     if (p.stat_part) return RYOLO_EINVAL;
-    RYOLO_CONV_DRY_RUN(lc, code);
     return launch_kernel<conv_igemm_persist_kernel<KS, BM, BN, WGM, WGN, false>>(g, b, smem, lc.stream, p, BnRed());
 }
 
-template <int KS, int BM, int BN, int WGM, int WGN, int NSTAGE = 2>
-int launch_variant(ConvParams &p, const ConvLaunch &lc) {
-    const bool gen = p.stat_part != nullptr || p.os != 1;
-    {
-        const long long dmax = p.Wo > p.Ho ? p.Wo : p.Ho, mpad = ((long long)p.M + BM - 1) / BM * BM;
+// IGEMM_TILES[I], I + 1 ... -> the plan's tile: the divisions its kernels make, then the plan's grid
+template <int KS, int I = 0>
+int launch_igemm_tile(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc) {
+    if constexpr (I < IGEMM_NTILES) {
+        constexpr IgemmTile T = IGEMM_TILES[I];
+        if (pl.kernel != RYOLO_CONV_KERNEL_IGEMM + T.code) return launch_igemm_tile<KS, I + 1>(pl, p, lc);
+        const bool gen = p.stat_part != nullptr || p.os != 1;
+        const long long dmax = p.Wo > p.Ho ? p.Wo : p.Ho, mpad = ((long long)p.M + T.BM - 1) / T.BM * T.BM;
         p.use_magic = mpad * dmax < 0x100000000ll ? 1 : 0;
         p.magic_wo = magic_u32(p.Wo);
         p.magic_ho = magic_u32(p.Ho);
+        p.nt = (p.Cout + T.BN - 1) / T.BN;
+        if constexpr (igemm_persist_tile(T)) if (pl.persist) return launch_persist<KS, I>(pl, p, lc);
+        if (pl.persist) return RYOLO_EINVAL;
+        if (p.fast) return gen ? launch_one_tile<KS, I, true, true>(pl, p, lc) : launch_one_tile<KS, I, true, false>(pl, p, lc);
+        return gen ? launch_one_tile<KS, I, false, true>(pl, p, lc) : launch_one_tile<KS, I, false, false>(pl, p, lc);
+    } else {
+        return RYOLO_EINVAL;
     }
-    // measured (tools/layer_bench.py, MI355X): the persistent grid wins on the short-K 1x1 layers (fixed per-tile cost
-    // dominates: 64->32 @304 0.146 -> 0.112 ms, 256->128 @76 0.034 -> 0.031) and loses 3-5 % on the long-K 3x3 layers
-    // (0.120 -> 0.127 ms), so only the 1x1 instantiations take it unless tile bit 0x800 forces it
-    // (the training forward of a 1x1 layer takes it too: the 4-wave tiles have a statistics instantiation)
-    const bool persist_ok = p.os == 1 && (!p.stat_part || (WGM * WGN == 4 && !p.res));
-    if constexpr (NSTAGE == 2 && BM * BN * 2 <= (BM + BN) * BK * 2) if (p.fast && persist_ok && !p.no_persist && (KS == 1 || p.force_persist)) {
-        // ... when the tile list is deep enough and the multiply-high divisions are exact (persist_grid), with the 4-wave layout
-        // (the 8-wave persistent variant is slower: 0.031)
-        const PersistGrid pg = persist_grid(p.M, BM, p.Cout, BN, p.Ho, p.Wo, p.force_persist != 0);
-        if (pg.deep && pg.exact) {
-            p.nt = pg.nt;
-            p.ntiles = (int)pg.tiles;
-            p.magic_nt = magic_u32(pg.nt);
-            return launch_persist<KS, BM, BN, WGM, WGN>(p, pg.grid, lc);
-        }
-    }
-    if (p.fast) {
-        if (gen) return launch_variant_impl<KS, BM, BN, WGM, WGN, NSTAGE, true, true>(p, lc);
-        return launch_variant_impl<KS, BM, BN, WGM, WGN, NSTAGE, true, false>(p, lc);
-    }
-    if (gen) return launch_variant_impl<KS, BM, BN, WGM, WGN, NSTAGE, false, true>(p, lc);
-    return launch_variant_impl<KS, BM, BN, WGM, WGN, NSTAGE, false, false>(p, lc);
 }
 
 }  // namespace
 
-// ---- the tuning switches of the shipped library (conv_common.h: TuneKey).  One getenv per switch, once.
-static const char *const TUNE_NAMES[TUNE_COUNT] = {"RYOLO_CONV3X3", "RYOLO_CONV1X1", "RYOLO_RNMS_TILES", "RYOLO_MQ_KORDER", "RYOLO_BN_REDUCE_TILES",
-                                                   "RYOLO_STEM_DGRAD"};
-static char g_tune_val[TUNE_COUNT][24];
-static bool g_tune_set[TUNE_COUNT];
-static std::once_flag g_tune_once;
-static void tune_store(int k, const char *v) {
-    g_tune_set[k] = v != nullptr && v[0] != 0;
-    if (g_tune_set[k]) {
-        strncpy(g_tune_val[k], v, sizeof(g_tune_val[k]) - 1);
-        g_tune_val[k][sizeof(g_tune_val[k]) - 1] = 0;
-    }
-}
-static void tune_init() {
-    for (int k = 0; k < TUNE_COUNT; k++) tune_store(k, getenv(TUNE_NAMES[k]));
-}
-namespace ryolo_detail {
-const char *tune(TuneKey k) {
-    std::call_once(g_tune_once, tune_init);
-    return g_tune_set[k] ? g_tune_val[k] : nullptr;
-}
-}  // namespace ryolo_detail
-extern "C" int ryolo_set_tuning(const char *name, const char *value) {
-    if (!name) return RYOLO_EINVAL;
-    std::call_once(g_tune_once, tune_init);
-    for (int k = 0; k < TUNE_COUNT; k++)
-        if (!strcmp(name, TUNE_NAMES[k])) {
-            tune_store(k, value);         // (not synchronised with launches in flight on other threads: a test / A-B facility)
-            return RYOLO_OK;
+// measured (tools/layer_bench.py, MI355X): the persistent grid wins on the short-K 1x1 layers (fixed per-tile cost
+// dominates: 64->32 @304 0.146 -> 0.112 ms, 256->128 @76 0.034 -> 0.031) and loses 3-5 % on the long-K 3x3 layers
+// (0.120 -> 0.127 ms), so only the 1x1 launches take it unless the caller forces it -- when the tile list is deep enough and the
+// multiply-high divisions are exact (persist_grid), with the 4-wave layout (the 8-wave persistent variant is slower: 0.031)
+// (the training forward of a 1x1 layer takes it too: the 4-wave tiles have a statistics instantiation)
+bool ryolo_detail::conv_igemm_plan(const ConvParams &p, int ksize, int tile, bool no_persist, bool force_persist, bool reduce, ConvPlan &pl) {
+    const IgemmTile *t = igemm_tile(tile);
+    if (!t || (ksize != 1 && ksize != 3)) return false;
+    const bool gen = p.stat_part != nullptr || p.os != 1;
+    const bool persist_ok = p.os == 1 && (!p.stat_part || (t->WGM * t->WGN == 4 && !p.res));
+    const int mtiles = (p.M + t->BM - 1) / t->BM, nt = (p.Cout + t->BN - 1) / t->BN;
+    pl.persist = false;
+    pl.grid = mtiles * nt;
+    if (igemm_persist_tile(*t) && p.fast && persist_ok && !no_persist && (ksize == 1 || force_persist)) {
+        const PersistGrid pg = persist_grid(p.M, t->BM, p.Cout, t->BN, p.Ho, p.Wo, force_persist);
+        if (pg.deep && pg.exact) {
+            pl.persist = true;
+            pl.grid = pg.grid;
         }
-    return RYOLO_EINVAL;
+    }
+    pl.rows = 0;
+    if (reduce) {
+        if (p.stat_part || p.ups != 1 || !igemm_reduce_tile(ksize, *t, pl.persist) || (!pl.persist && (!p.fast || gen))) return false;
+        pl.rows = pl.persist ? pl.grid : mtiles;
+    }
+    pl.kernel = RYOLO_CONV_KERNEL_IGEMM + tile;
+    return true;
+}
+
+int ryolo_detail::launch_conv_igemm(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc) {
+    return pl.ksize == 1 ? launch_igemm_tile<1>(pl, p, lc) : launch_igemm_tile<3>(pl, p, lc);
+}
+
+int ryolo_detail::launch_conv0_direct(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc) {
+    return p.stat_part ? launch_c8_direct<true>(p, pl.bm, (unsigned)pl.grid, lc.stream) : launch_c8_direct<false>(p, pl.bm, (unsigned)pl.grid, lc.stream);
 }
 
 extern "C" {
@@ -1453,371 +1430,6 @@ int ryolo_nhwc_bf16_to_nchw_f32(const void *x, int N, int C, int H, int W, int c
     hipLaunchKernelGGL(nhwc_bf16_to_nchw_f32_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const __bf16 *)x, N,
                        C, H, W, cstride, y);
     return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
-}
-
-}  // extern "C"
-
-static int pick_tile(const ryolo_conv_desc *d) {
-    return d->tile & 0xff;   // 0 = auto (dispatch decides); bit 8 (0x100) forces the general (slow-address) path, for tests
-}
-
-// Which 256-channel tile a 3x3 layer takes: conv_mp.hip (one 8-wave workgroup per CU, 256 or 192 pixel rows) or conv_mq.hip (two
-// 4-wave workgroups per CU, 128 rows).  Estimated launch time = (tiles of the busiest CU) x (time per tile), time per tile
-// linear in the K depth; coefficients (us, bs 32 / 608^2 layers with the fused shortcut, MI355X) from tools/mp_ablate.py,
-// profiles/r03_mp_vs_mq.txt.  conv_mq wins where the tile list is deep enough to keep both workgroups of every CU busy (the
-// 76^2 and 38^2 layers), conv_mp's 192-row tile where one round of tiles fills the chip better (19^2: 244 tiles on 256 CUs).
-// Returns 0 = conv_mq, else the BM of conv_mp.  RYOLO_CONV3X3 = mp | mq overrides (A/B timing, tests).
-static int pick_wide_tile(const ConvParams &p) {
-    const char *e = tune(TUNE_CONV3X3);
-    const int forced = !e ? 0 : (!strcmp(e, "mp") ? 1 : (!strcmp(e, "mq") ? 2 : 0));
-    if (forced == 2) return 0;
-    const int bm_mp = conv_mp_pick_bm(p);
-    if (forced == 1) return bm_mp;
-    // Cost model in microseconds, calibrated on tools/mp_ablate.py --exp mq at bs 32 and bs 64 (K tiles 18 / 36 / 72 = the 76^2 /
-    // 38^2 / 19^2 layers; piecewise linear in between, the last slope beyond):
-    //   conv_mp   rounds of the persistent grid x the time of one tile;
-    //   conv_mq   the busiest CU hosts workgroups `loc` and `loc + wgx/2` of an XCD with a >= b tiles: b tile slots run with both
-    //             workgroups resident (c2 per slot), the a - b slots after the partner has finished run alone at 0.7 c2.
-    const long long cus = cu_count() & ~7, nt = (p.Cout + 255) / 256, kt = p.Kpad / BK;
-    auto interp = [&](double v18, double v36, double v72) {
-        return kt <= 36 ? v18 + (kt - 18) * (v36 - v18) / 18.0 : v36 + (kt - 36) * (v72 - v36) / 36.0;
-    };
-    auto rounds = [&](int bm) { return ((((long long)p.M + bm - 1) / bm) * nt + cus - 1) / cus; };
-    const double t256 = rounds(256) * interp(35.5, 59.5, 102.0), t192 = rounds(192) * interp(30.5, 53.0, 92.0);
-    // conv_mq: XCD chunks of the tile list, 2 x cus / 8 workgroups per XCD, CU c hosts workgroups c and c + cus / 8
-    const long long tq = ((((long long)p.M + 127) / 128) * nt + 7) / 8, wgx = 2 * cus / 8;
-    auto ntile = [&](long long loc) { return loc < tq ? (tq - loc + wgx - 1) / wgx : 0; };
-    const double c2 = interp(32.5, 59.0, 97.0);
-    const double tq_ = (double)ntile(wgx / 2) * c2 + (double)(ntile(0) - ntile(wgx / 2)) * 0.7 * c2;
-    if (tq_ < t256 && tq_ < t192) return 0;
-    return t192 < t256 ? 192 : 256;
-}
-
-static long long g_nt_out_min = NT_OUT_MIN_BYTES;      // (settable in ablation builds: ryolo_debug_conv_nt_min)
-// (measurement build: RYOLO_NT_OUT_MIN_MB overrides the threshold (MiB) per call -- the in-chain sweep of tools/step_ab.py, profiles/r05_ab_log.txt)
-long long ryolo_detail::nt_out_min_bytes() {
-    const char *e = abl_env("RYOLO_NT_OUT_MIN_MB");
-    return e ? (long long)atoll(e) << 20 : g_nt_out_min;
-}
-// (sc1 write-through stores for the outputs below that threshold -- no dirty lines left in L2 at the kernel boundary -- were tried in the chain
-// in round 5 and lost: bs-32 forward 6.105 ms default / 6.148 from 32 MiB / 6.191 from 8 MiB / 6.130 everywhere, profiles/r05_ab_log.txt; removed)
-#ifdef RYOLO_MP_ABLATION
-extern "C" void ryolo_debug_conv_nt_min(long long bytes) { g_nt_out_min = bytes; }
-#endif
-
-// RYOLO_CONV1X1 = igemm keeps the 1x1 layers on the 128 x 128 tiles (A/B timing; ryolo_set_tuning)
-bool ryolo_detail::conv_pw_disabled() {
-    const char *e = tune(TUNE_CONV1X1);
-    return e && !strcmp(e, "igemm");
-}
-
-// conv_mq.hip's 128-channel tiles (round 5).  RYOLO_MQ128 = 0 (default): off -- the 128 x 128 / 256 x 64 tiles of this file as in round 4;
-// 1: the 3x3 layers and data gradients with C_out % 256 != 0; 2: also the 1x1 layers whose 128-pixel tile list is short (38^2 / 19^2).
-// OPT-IN because they measure no faster than the tiles they would replace (profiles/r05_mq128_bench.txt, r05_ab_log.txt: bs-64 step 49.27 ms
-// off / 49.59 on / 49.85 with the 1x1 layers; bs-32 forward 6.08 / 6.07 / 6.30 ms): with 32 channels per wave a K tile moves 0.625 KiB of
-// LDS fragments per MFMA against 0.375 for the 256-channel tile -- the LDS pipe, not the schedule, bounds these layers.
-// MEASUREMENT BUILD ONLY (round 6): the shipped library has neither the switch nor the instantiations (launch_conv_mq128 returns EINVAL).
-int ryolo_detail::mq128_knob() {
-    const char *e = abl_env("RYOLO_MQ128");
-    return e ? atoi(e) : 0;
-}
-// pixels per tile: 64 when the list of 128-pixel tiles is less than 2.5 rounds of the two-workgroups-per-CU grid deep
-static int mq128_pick_bm(const ConvParams &p) {
-    return persist_grid(p.M, 128, p.Cout, 128, p.Ho, p.Wo).deep ? 128 : 64;
-}
-// does the auto dispatch send this launch to the 128-channel family?  (3x3: every eligible shape the 256-channel tiles do not serve;
-// 1x1 (knob 2): K >= 256 and a short tile list -- the 76^2 layers stay on conv_pw.hip, HBM-bound and at their floor there)
-static bool mq128_auto(const ConvParams &p, int ksize) {
-    const int knob = mq128_knob();
-    if (knob <= 0 || !conv_mq128_eligible(p)) return false;
-    if (ksize == 3) return !conv_mp_eligible(p);
-    if (knob < 2 || p.Kpad < 4 * BK) return false;
-    return !persist_grid(p.M, 128, p.Cout, 128, p.Ho, p.Wo, false, 8).deep;      // fewer than FOUR rounds of 128-pixel tiles
-}
-
-// RYOLO_CONV0=direct keeps layer 0 on conv3x3_c8_direct_kernel (fragments from global memory); default: the LDS-staged kernel of
-// conv_stem.hip (measurement build only since round 6: A/B timing)
-static bool conv0_halo_on() {
-    const char *e = abl_env("RYOLO_CONV0");
-    return !(e && !strcmp(e, "direct"));
-}
-
-int ryolo_detail::dispatch(ConvParams &p, int ksize, int pick, const ConvLaunch &lc) {
-    const BnRed *const bnred = lc.bnred;
-    // the stem kernel (conv_stem.hip: 3x3, 32 -> 64 channels, input patch staged once): auto and pick 12
-    const bool stem = (pick == 0 || pick == 12) && conv_stem_eligible(p, ksize) && !bnred;
-    if (pick == 12 && !stem) return RYOLO_EINVAL;
-    if (bnred && lc.bnred_mode == 3) p.no_persist = 1;          // the reduce rides in the one-tile-per-workgroup kernel
-    // the weight-stationary 1x1 kernel (conv_pw.hip): auto and pick 13; RYOLO_CONV1X1 = igemm keeps the 128x128 tiles (A/B timing, tests)
-    const bool pw = ((pick == 0 && !conv_pw_disabled()) || pick == 13) && conv_pw_eligible(p, ksize) && (pick == 13 || (bnred ? lc.bnred_mode == 1 : conv_pw_preferred(p)));
-    if (pick == 13 && !pw) return RYOLO_EINVAL;
-    if (stem) return launch_conv_stem(p, lc);
-    // conv_stem.hip's 3x3 / 1 64 -> 128 kernel (round 6): auto and pick 17 (measurement build: RYOLO_STEM64=0 keeps the 128 x 128 tiles, A/B timing)
-    {
-        const char *e64 = abl_env("RYOLO_STEM64");
-        const bool stem64 = ((pick == 0 && !(e64 && !strcmp(e64, "0"))) || pick == 17) && conv_stem64_eligible(p, ksize) && !bnred;
-        if (pick == 17 && !stem64) return RYOLO_EINVAL;
-        if (stem64) return launch_conv_stem64(p, lc);
-    }
-    // conv_mq.hip's 128-channel tiles: picks 15 (128 pixels) / 16 (64 pixels); auto per mq128_auto(); with the folded reduce only as
-    // bnreduce_plan's mode 4 (its caller sized the partial rows for that grid)
-    if (pick == 15 || pick == 16) {
-        ConvLaunch l = lc;
-        if (lc.bnred_mode != 4) l.bnred = nullptr;
-        return launch_conv_mq128(p, pick == 15 ? 128 : 64, l);
-    }
-    if (pick == 0 && (bnred ? lc.bnred_mode == 4 : mq128_auto(p, ksize))) {
-        const int r = launch_conv_mq128(p, mq128_pick_bm(p), lc);
-        if (r != RYOLO_EINVAL || bnred) return r;              // EINVAL: a size guard -- the tiles below take those
-    }
-    if (pw) {
-        const int r = launch_conv_pw(p, lc);
-        if (r != RYOLO_EINVAL || pick == 13 || bnred) return r;      // EINVAL: a size guard (2 GiB slices) -- the 128x128 tiles take those
-                                                                        // (not with the folded reduce: its caller sized the partial rows for THIS grid)
-    }
-    if (pick == 0) {
-        // auto: 3x3 layers with 256-multiple output channels take one of the persistent multi-phase tiles (the 1x1 layers are
-        // faster on the 128x128 tiles, tools/mp_tune.py)
-        if (ksize == 3 && conv_mp_eligible(p) && !bnred) {
-            const int bm = pick_wide_tile(p);
-            const int r = bm == 0 ? launch_conv_mq(p, 0, lc) : launch_conv_mp(p, bm, 0, lc);
-            if (r != RYOLO_EINVAL) return r;      // EINVAL: a size guard of the persistent tiles (2 GiB output slices, 2^32 pixel*extent) -- the 128x128 tiles take those
-        }
-        pick = p.Cout <= 32 ? 3 : (p.Cout <= 64 ? 2 : 1);
-        // 3x3 layers with a short K loop (C_in <= 64: at most 9 K steps) are all tile prologue / epilogue on the one-tile-per-
-        // workgroup grid; the persistent 4-wave tiles prefetch the next tile's first K step under the epilogue (measured bs 32:
-        // 3x3/2 32->64@304 0.339 -> 0.297 ms, 3x3 64->128@152 0.151 -> 0.136, 3x3/2 64->128@152 0.178 -> 0.165; long-K layers lose)
-        // (not the statistics instantiation of the 256 x 64 tile: under the two-workgroup register cap it spills 54 VGPRs and runs
-        // 2.2 x slower than the one-tile grid; with 512 registers and one workgroup per CU it is no faster than that grid either)
-        if (ksize == 3 && p.os == 1 && p.fast && p.Kpad / BK <= 9 && !p.no_persist && !(p.stat_part && (p.res || pick == 2))) {
-            p.force_persist = 1;
-            if (pick == 1) pick = 7;
-        }
-    }
-    // picks 8 / 11 / 14: the 256-channel multi-phase tile of conv_mp.hip with BM 256 / BM 192 / BM picked per shape (tests, A/B timing)
-    if (pick == 8) return launch_conv_mp(p, 256, 0, lc);
-    if (pick == 11) return launch_conv_mp(p, 192, 0, lc);
-    if (pick == 14) return launch_conv_mp(p, 0, 0, lc);
-    if (pick == 9) return launch_conv_mq(p, 0, lc);      // the two-workgroups-per-CU tile of conv_mq.hip
-#ifdef RYOLO_MP_ABLATION
-    if (pick >= 32 && pick < 64) return launch_conv_mp(p, (pick & 16) ? 192 : 256, ryolo_mp_ablation_variant(pick & 15), lc);
-    if (pick >= 64 && pick < 80) return launch_conv_mq(p, ryolo_mp_ablation_variant(pick & 15), lc);
-#endif
-    if (ksize == 1) {
-        if (pick == 1) {   // 8 waves of 64 pixels x 32 channels, except where the (4-wave) persistent grid wins
-            if (p.fast && p.os == 1 && !(p.stat_part && p.res) && !p.no_persist && (p.force_persist || persist_grid(p.M, 128, p.Cout, 128, p.Ho, p.Wo).deep))
-                return launch_variant<1, 128, 128, 2, 2>(p, lc);
-            p.no_persist = 1;
-            return launch_variant<1, 128, 128, 2, 4>(p, lc);
-        }
-        if (pick == 7) return launch_variant<1, 128, 128, 2, 2>(p, lc);
-        if (pick == 2) return launch_variant<1, 256, 64, 4, 1>(p, lc);
-        if (pick == 3) return launch_variant<1, 256, 32, 4, 1>(p, lc);
-        if (pick == 4) return launch_variant<1, 256, 128, 4, 2, 3>(p, lc);
-        if (pick == 6) return launch_variant<1, 128, 128, 4, 2>(p, lc);
-    } else {
-        if (pick == 1) return launch_variant<3, 128, 128, 2, 4>(p, lc);
-        if (pick == 7) return launch_variant<3, 128, 128, 2, 2>(p, lc);
-        if (pick == 2) return launch_variant<3, 256, 64, 4, 1>(p, lc);
-        if (pick == 3) return launch_variant<3, 256, 32, 4, 1>(p, lc);
-        if (pick == 4) return launch_variant<3, 256, 128, 4, 2, 3>(p, lc);
-        if (pick == 6) return launch_variant<3, 128, 128, 4, 2>(p, lc);
-    }
-    return RYOLO_EINVAL;
-}
-
-int ryolo_detail::conv_validate(const ryolo_conv_desc *d) {
-    if (!d) return RYOLO_EINVAL;
-    if (d->ksize != 1 && d->ksize != 3) return RYOLO_EINVAL;
-    if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->stride <= 0) return RYOLO_EINVAL;
-    if ((d->Cin & 7) || (d->Cout & 7) || (d->in_cstride & 7) || (d->out_cstride & 7)) return RYOLO_EINVAL;
-    if (d->in_cstride < d->Cin || d->out_cstride < d->Cout) return RYOLO_EINVAL;
-    if (d->upsample != 1 && d->upsample != 2) return RYOLO_EINVAL;
-    if (d->ksize == 1 && d->pad != 0) return RYOLO_EINVAL;
-    return RYOLO_OK;
-}
-
-// The shape part of a launch from its descriptor: tensor geometry, the GEMM sizes, the regular tap window, dense output placement, the
-// epilogue.  Everything else of `p` is the caller's (value-initialised: what a path does not set is zero).  False: no output pixels, or
-// more than the 31-bit pixel index holds.
-static bool conv_shape(const ryolo_conv_desc *d, ConvParams &p) {
-    p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.in_cs = d->in_cstride;
-    p.stride = d->stride; p.pad = d->pad;
-    p.Ho = (d->H + 2 * d->pad - d->ksize) / d->stride + 1;
-    p.Wo = (d->W + 2 * d->pad - d->ksize) / d->stride + 1;
-    if (p.Ho <= 0 || p.Wo <= 0) return false;
-    p.Cout = d->Cout; p.out_cs = d->out_cstride; p.res_cs = d->res_cstride;
-    p.K = d->ksize * d->ksize * d->Cin;
-    p.Kpad = (p.K + BK - 1) / BK * BK;
-    const long long M = (long long)d->N * p.Ho * p.Wo;
-    if (M > 0x7fffffffLL - 512) return false;
-    p.M = (int)M;
-    p.ntaps = d->ksize * d->ksize;
-    for (int t = 0; t < 9; t++) { p.tap_dy[t] = t / d->ksize; p.tap_dx[t] = t % d->ksize; }
-    p.os = 1; p.osx = 1; p.ooy = 0; p.oox = 0; p.OH = p.Ho; p.OW = p.Wo;
-    p.act = d->act; p.slope = d->slope; p.ups = d->upsample;
-    return true;
-}
-
-// Darknet-53 layer 0 as conv3x3_c8_direct_kernel / conv0_halo_kernel serve it: 3x3 / 1 pad 1, 8 (padded) -> 32 channels, rows of at
-// least 16 pixels, 32-bit buffer offsets over x and y (out_cs: the pixel stride of what the launch writes)
-static bool conv0_shape(const ryolo_conv_desc *d, int out_cs) {
-    const unsigned long long M = (unsigned long long)d->N * d->H * d->W;
-    return d->ksize == 3 && d->stride == 1 && d->pad == 1 && d->Cin == 8 && d->in_cstride == 8 && d->Cout == 32 && d->upsample == 1 &&
-           !(d->tile & 0x1ff) && d->W >= 16 && buffer_extent(M, 8, 8) && buffer_extent(M, out_cs, 32);
-}
-// ... and its launch: the two descriptors (the second one covers y), 16-pixel groups, gpw of them per wave, 4 waves per block
-static bool conv0_params(const ryolo_conv_desc *d, int out_cs, ConvParams &p, int gpw, unsigned *nblk) {
-    if (!conv_shape(d, p) || !buffer_extent(p.M, 8, 8, &p.x_bytes) || !buffer_extent(p.M, out_cs, 32, &p.w_bytes)) return false;
-    p.out_cs = out_cs; p.res_cs = 0;
-    p.nt_out = (long long)p.M * 64 >= nt_out_min_bytes() ? 1 : 0;
-    const long long groups = ((long long)p.M + 15) / 16, waves = (groups + gpw - 1) / gpw;
-    *nblk = (unsigned)((waves + 3) / 4);
-    return true;
-}
-
-// the forward launch behind ryolo_conv2d_bn_act_stats and ryolo_conv_kernel_choice (lc.choice: only whether residual / stat_part are
-// null matters then -- nothing is dereferenced before the launch site)
-static int conv_forward(const ryolo_conv_desc *d, const void *x, const void *w_packed, const float *scale, const float *shift,
-                        const void *residual, void *y, double *stat_part, const ConvLaunch &lc) {
-    if (conv_validate(d) != RYOLO_OK) return RYOLO_EINVAL;
-    if (residual && ((d->res_cstride & 7) || d->res_cstride < d->Cout)) return RYOLO_EINVAL;
-    ConvParams p{};
-    p.x = (const __bf16 *)x;
-    p.w = (const __bf16 *)w_packed;
-    p.scale = scale;
-    p.shift = shift;
-    p.res = (const __bf16 *)residual;
-    p.y = (__bf16 *)y;
-    p.stat_part = stat_part;
-    if (!residual && conv0_shape(d, d->out_cstride)) {
-        // Darknet-53 layer 0: fragments straight from global memory (conv3x3_c8_direct_kernel); 32-bit buffer offsets
-        const int gpw = (d->tile >> 16) ? (d->tile >> 16) : 32;   // groups of 16 pixels per wave (upper tile bits: tuning)
-        unsigned nblk;
-        if (!conv0_params(d, d->out_cstride, p, gpw, &nblk)) return RYOLO_EINVAL;
-        p.cin_log2 = 3;
-        p.stat_cpad = 128;
-        const bool staged = conv0_halo_on() && !(d->tile >> 16) && y && !stat_part;
-        RYOLO_CONV_DRY_RUN(lc, (staged ? RYOLO_CONV_KERNEL_STEM0 : RYOLO_CONV_KERNEL_DIRECT8));
-        // (the statistics-only pass stays on the direct kernel: 284 us against 320 for the staged one -- that pass is bound by its per-element
-        // arithmetic, not by the fragment path)
-        // (... and so do the statistics of the stored-z form: the two statistics passes must add the same values in the same order)
-        if (staged) return launch_conv0_halo(p, nullptr, 0, lc);
-        return stat_part ? launch_c8_direct<true>(p, gpw, nblk, lc.stream) : launch_c8_direct<false>(p, gpw, nblk, lc.stream);
-    }
-    if (!conv_shape(d, p)) return RYOLO_EINVAL;
-    p.cin_log2 = ilog2_exact(d->Cin);
-    if (d->ksize == 3 && p.cin_log2 < 0 && (d->Cin % BK)) return RYOLO_EINVAL;
-    p.taps2 = (d->Cin == 32 && d->ksize == 3) ? 1 : 0;
-    p.fast = (d->Cin % BK == 0 || p.taps2) && !(d->tile & 0x100) && buffer_extent((unsigned long long)d->N * d->H * d->W, d->in_cstride, d->Cin, &p.x_bytes) &&
-             buffer_extent((d->Cout + 127) / 128 * 128, p.Kpad, p.Kpad + 128, &p.w_bytes);
-    if (!p.fast) p.taps2 = p.x_bytes = p.w_bytes = 0;
-    p.no_persist = (d->tile & 0x200) ? 1 : 0;
-    p.force_persist = (d->tile & 0x800) ? 1 : 0;
-    p.pw_grid_cap = (d->tile & 0xff) == 13 ? (d->tile >> 16) & 0xff : 0;
-#ifdef RYOLO_MP_ABLATION
-    if ((d->tile & 0x400) && p.fast) p.x_bytes = p.w_bytes = 0;   // timing experiment: every load out of range (zeros, no traffic)
-#endif
-    p.nt_out = (long long)p.M * d->upsample * d->upsample * d->Cout * 2 >= nt_out_min_bytes() ? 1 : 0;
-    p.stat_cpad = (d->Cout + 127) / 128 * 128;
-    return dispatch(p, d->ksize, pick_tile(d), lc);
-}
-
-// a YOLO head as conv_pw.hip's decode launch sees it: 1x1 / 1, K = C_in a multiple of 64, dense output rows
-static bool head_params(const ryolo_conv_desc *d, ConvParams &p) {
-    if (conv_validate(d) != RYOLO_OK || d->ksize != 1 || d->stride != 1 || d->pad != 0 || d->upsample != 1 || (d->Cin % BK)) return false;
-    if (!conv_shape(d, p)) return false;
-    p.out_cs = d->Cout; p.res_cs = 0; p.Kpad = d->Cin;
-    if (!buffer_extent(p.M, d->in_cstride, d->Cin, &p.x_bytes) || !buffer_extent((d->Cout + 127) / 128 * 128, p.Kpad, p.Kpad + 128, &p.w_bytes)) return false;
-    p.fast = 1; p.use_magic = 1;
-    return true;
-}
-
-extern "C" {
-
-int ryolo_conv_stat_rows(const ryolo_conv_desc *d) {
-    if (conv_validate(d) != RYOLO_OK) return 0;
-    return STAT_ROWS;
-}
-
-int ryolo_conv2d_bn_act_stats(const ryolo_conv_desc *d, const void *x, const void *w_packed, const float *scale,
-                              const float *shift, const void *residual, void *y, double *stat_part, void *stream_) {
-    if (!x || !w_packed || !scale || !shift) return RYOLO_EINVAL;
-    if (!y && !(stat_part && ryolo_conv0_recompute_supported(d))) return RYOLO_EINVAL;     // y == NULL: statistics only, layer-0 kernel only
-    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w_packed | (uintptr_t)residual | (uintptr_t)scale | (uintptr_t)shift) & 15)
-        return RYOLO_EINVAL;
-    ConvLaunch lc;
-    lc.stream = (hipStream_t)stream_;
-    return conv_forward(d, x, w_packed, scale, shift, residual, y, stat_part, lc);
-}
-
-int ryolo_conv2d_bn_act(const ryolo_conv_desc *d, const void *x, const void *w_packed, const float *scale,
-                        const float *shift, const void *residual, void *y, void *stream_) {
-    return ryolo_conv2d_bn_act_stats(d, x, w_packed, scale, shift, residual, y, nullptr, stream_);
-}
-
-int ryolo_conv_kernel_choice(const ryolo_conv_desc *d, int with_residual, int with_statistics) {
-    int choice = -1;
-    ConvLaunch lc;
-    lc.choice = &choice;
-    void *fake = (void *)(uintptr_t)4096;      // never dereferenced: the dispatch returns before any launch
-    const int rc = conv_forward(d, fake, fake, (const float *)fake, (const float *)fake, with_residual ? fake : nullptr, fake,
-                                with_statistics ? (double *)fake : nullptr, lc);
-    return rc == RYOLO_OK ? choice : -1;
-}
-
-int ryolo_conv_head_decode_supported(const ryolo_conv_desc *d, int na, int no) {
-    ConvParams p{};
-    return head_params(d, p) && conv_pw_decode_supported(p, na, no) ? 1 : 0;
-}
-
-int ryolo_conv_head_decode(const ryolo_conv_desc *d, const void *x, const void *w_packed, const float *scale, const float *shift,
-                           const float *anchors, int na, int no, float stride, float context_factor, int arc, float *io,
-                           long long io_rows_per_image, long long io_row_offset, float *pout, void *stream_) {
-    ConvParams p{};
-    if (!x || !w_packed || !scale || !shift || !anchors || !io || !head_params(d, p) || !conv_pw_decode_supported(p, na, no)) return RYOLO_EINVAL;
-    if (arc < 0 || arc > 2 || !(stride > 0.f) || !(context_factor > 0.f)) return RYOLO_EINVAL;
-    if (((uintptr_t)x | (uintptr_t)w_packed) & 15) return RYOLO_EINVAL;
-    p.x = (const __bf16 *)x; p.w = (const __bf16 *)w_packed; p.scale = scale; p.shift = shift;
-    return launch_conv_pw_decode(p, io, io_rows_per_image, io_row_offset, pout, anchors, na, no, stride, context_factor, arc, (hipStream_t)stream_);
-}
-
-int ryolo_conv_head_decode_store(const ryolo_conv_desc *d, const void *x, const void *w_packed, const float *scale, const float *shift,
-                                 int na, int no, void *head, int head_cstride, float *pout, void *stream_) {
-    ConvParams p{};
-    if (!x || !w_packed || !scale || !shift || !head || !pout || !head_params(d, p) || !conv_pw_decode_supported(p, na, no)) return RYOLO_EINVAL;
-    if (((uintptr_t)x | (uintptr_t)w_packed) & 15) return RYOLO_EINVAL;
-    p.x = (const __bf16 *)x; p.w = (const __bf16 *)w_packed; p.scale = scale; p.shift = shift;
-    return launch_conv_pw_decode(p, nullptr, 0, 0, pout, nullptr, na, no, 1.f, 1.f, 0, (hipStream_t)stream_, head, head_cstride);
-}
-
-int ryolo_conv_pair_supported(const ryolo_conv_desc *first, const ryolo_conv_desc *second, int shortcut_from_input) {
-    if (conv_validate(first) != RYOLO_OK || conv_validate(second) != RYOLO_OK) return 0;
-    return conv_stem_pair_kind(first, second, shortcut_from_input) != 0 ? 1 : 0;
-}
-
-int ryolo_conv2d_bn_act_pair(const ryolo_conv_desc *a, const ryolo_conv_desc *b, const void *x, const void *w_first, const float *scale_first,
-                             const float *shift_first, const void *w_second, const float *scale_second, const float *shift_second,
-                             int shortcut_from_input, void *y, void *stream_) {
-    if (conv_validate(a) != RYOLO_OK || conv_validate(b) != RYOLO_OK || !x || !w_first || !scale_first || !shift_first || !w_second || !scale_second ||
-        !shift_second || !y)
-        return RYOLO_EINVAL;
-    const int kind = conv_stem_pair_kind(a, b, shortcut_from_input);
-    if (!kind) return RYOLO_EINVAL;
-    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w_first | (uintptr_t)w_second) & 15) return RYOLO_EINVAL;
-    ConvParams p{};           // the second layer; its input is the first layer's output in LDS: dense, never in memory
-    if (!conv_shape(b, p)) return RYOLO_EINVAL;
-    p.w = (const __bf16 *)w_second; p.scale = scale_second; p.shift = shift_second; p.y = (__bf16 *)y;
-    p.in_cs = b->Cin; p.res_cs = 0;
-    p.nt_out = (long long)p.M * b->Cout * 2 >= nt_out_min_bytes() ? 1 : 0;
-    const unsigned long long xb = (((unsigned long long)a->N * a->H * a->W - 1) * a->in_cstride + a->Cin) * 2ull;   // (< 2^31: conv_stem_pair_kind)
-    const int kpad_first = (a->ksize * a->ksize * a->Cin + BK - 1) / BK * BK;
-    return launch_conv_stem_pair(kind, p, x, (unsigned)xb, a->in_cstride, a->H, a->W, w_first, kpad_first, scale_first, shift_first, a->act,
-                                 a->slope, (hipStream_t)stream_);
-}
-
-int ryolo_conv0_recompute_supported(const ryolo_conv_desc *d) {
-    return conv_validate(d) == RYOLO_OK && conv0_shape(d, d->out_cstride) ? 1 : 0;
 }
 
 int ryolo_conv0_bn_act_fwd(const ryolo_conv_desc *d, const void *x, const void *w_packed, const float *scale, const float *shift,

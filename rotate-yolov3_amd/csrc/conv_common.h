@@ -1,9 +1,11 @@
 // rotate-yolov3_amd/csrc/conv_common.h -- types, device helpers and host launch helpers shared by the convolution translation units
 // (and, for the types and launch helpers, by the training units wgrad.hip and train.hip):
-// conv.hip (128x128 / 256x64 / 256x32 tiles, first-layer direct kernel, dispatch() and the forward entry points), conv_dgrad.hip (data
-// gradient: tap classes, packers, the folded BatchNorm-reduce plan), conv_mp.hip (256-wide multi-phase kernel), conv_mq.hip (two
-// workgroups per CU), conv_pw.hip (weight-stationary 1x1), conv_stem.hip (stem layers).  Internal to libryolo_hip.so; the C ABI is
-// include/ryolo.h.
+// conv.hip (128x128 / 256x64 / 256x32 tiles, first-layer direct kernel, packers), conv_mp.hip (256-wide multi-phase kernel), conv_mq.hip
+// (two workgroups per CU), conv_pw.hip (weight-stationary 1x1), conv_stem.hip (stem layers) -- the kernel families, each with a planning
+// function (does the family serve this launch? every eligibility rule and size guard, nothing written) and a launch function (derives
+// what its kernel reads, picks the instantiation, launches); conv_dispatch.hip (host only: descriptor -> ConvParams, conv_plan() over the
+// families in order, conv_launch(), the forward entry points and queries); conv_dgrad.hip (data gradient: tap classes, packers, its
+// launches built through the same shape code and planned by conv_plan()).  Internal to libryolo_hip.so; the C ABI is include/ryolo.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -185,28 +187,41 @@ __device__ __forceinline__ void split_pixel(int m, int Wo, int Ho, unsigned magi
 
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
-// What a launch needs besides its ConvParams, passed explicitly from the entry point through dispatch() to every launcher.
-//   bnred / bnred_mode  ryolo_conv2d_dgrad_bnreduce: the launch must carry the folded BatchNorm-backward reduce, in the kernel
-//                       bnreduce_plan chose (its caller sized the partial rows for that launch): 1 conv_pw.hip's MODE 3, 2 the persistent
-//                       2x2 tile (one row per workgroup), 3 a one-tile-per-workgroup tile (one row per pixel tile), 4 conv_mq.hip's
-//                       128-channel tiles (one row per workgroup)
-//   choice              ryolo_conv_kernel_choice() / ryolo_conv_dgrad_kernel_choice(): a dry run of the dispatch.  Every launcher writes
-//                       the code of the kernel it is about to launch there and returns RYOLO_OK instead of launching -- the decision is
-//                       reported from the launch site itself, behind every size guard and fall-through, not from a parallel copy of the
-//                       decision tree
+// What a launch needs besides its ConvParams and its plan: the stream, and the operands of the folded BatchNorm-backward reduce when the
+// plan carries one (plan.rows > 0: ryolo_conv2d_dgrad_bnreduce)
 struct ConvLaunch {
     hipStream_t stream = nullptr;
     const BnRed *bnred = nullptr;
-    int bnred_mode = 0;
-    int *choice = nullptr;
 };
-#define RYOLO_CONV_DRY_RUN(lc, code)  \
-    do {                              \
-        if ((lc).choice) {            \
-            *(lc).choice = (code);    \
-            return RYOLO_OK;          \
-        }                             \
-    } while (0)
+
+// The six implicit-GEMM tiles of conv.hip, stated once: `code` is the tile as ryolo_conv_desc::tile forces it and as
+// RYOLO_CONV_KERNEL_IGEMM + code names it; BM pixels x BN channels, WGM x WGN waves, NSTAGE operand buffers
+struct IgemmTile {
+    int code, BM, BN, WGM, WGN, NSTAGE;
+};
+constexpr IgemmTile IGEMM_TILES[] = {{1, 128, 128, 2, 4, 2}, {2, 256, 64, 4, 1, 2}, {3, 256, 32, 4, 1, 2},
+                                     {4, 256, 128, 4, 2, 3}, {6, 128, 128, 4, 2, 2}, {7, 128, 128, 2, 2, 2}};
+constexpr int IGEMM_NTILES = sizeof(IGEMM_TILES) / sizeof(IGEMM_TILES[0]);
+constexpr const IgemmTile *igemm_tile(int code) {
+    for (int i = 0; i < IGEMM_NTILES; i++)
+        if (IGEMM_TILES[i].code == code) return &IGEMM_TILES[i];
+    return nullptr;
+}
+
+// Everything decided about one launch.  conv_plan() makes it -- a value, computed per call from the ConvParams alone, nothing kept
+// between calls -- and the queries (ryolo_conv_kernel_choice, ryolo_conv_dgrad_kernel_choice, ryolo_conv2d_dgrad_bnreduce_rows) read the
+// same plan conv_launch() executes.
+struct ConvPlan {
+    int kernel = -1;        // RYOLO_CONV_KERNEL_* (igemm: RYOLO_CONV_KERNEL_IGEMM + tile code); -1: no family serves the launch
+    int ksize = 0;
+    int bm = 0;             // pixel rows of the tile where a family has several (conv_mp 256 / 192, the 128-channel conv_mq 128 / 64);
+                            // layer 0: 16-pixel groups per wave
+    bool persist = false;   // igemm: the persistent grid
+    int grid = 0;           // workgroups
+    int rows = 0;           // with the folded BatchNorm reduce: rows of part[][3][C] the launch writes (one per workgroup of a persistent
+                            // launch, one per pixel tile of a one-tile-per-workgroup launch); 0: no reduce
+    int variant = 0;        // measurement build: schedule variant of conv_mp / conv_mq
+};
 
 // compute units of the current device (256 when it cannot be asked), read once
 inline int cu_count() {
@@ -241,8 +256,8 @@ inline bool buffer_extent(unsigned long long npix, long long cs, long long c, un
 // The persistent grid of the implicit-GEMM tiles over M pixels x Cout channels in BM x BN tiles: its size (two workgroups per CU, a
 // multiple of 8 for the XCD chunking), whether the tile list is deep enough for it to win -- at least rounds2 / 2 rounds (measured at 2.5:
 // 1444 tiles 0.030 -> 0.028 ms, 722 tiles 0.021 -> 0.022), or just more than one round when forced -- and whether the kernel's
-// multiply-high divisions are exact.  The ONE statement of that rule: dispatch(), launch_variant(), the conv_mq128 picks and bnreduce_plan
-// (which sizes the partial rows for the grid launched) all ask here.
+// multiply-high divisions are exact.  The one statement of that rule: conv_igemm_plan(), conv_plan()'s 1x1 pick and the conv_mq128 picks
+// ask here; the launch and the rows of a folded reduce read the plan.
 struct PersistGrid {
     int grid, nt;
     long long tiles;
@@ -259,6 +274,40 @@ inline PersistGrid persist_grid(long long M, int BM, int Cout, int BN, int Ho, i
     return g;
 }
 
+inline unsigned magic_u32(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }   // udiv_magic's operand
+
+// The tile list of a persistent conv_mp / conv_mq launch over bm-pixel x bn-channel tiles, and the extents of its output and residual
+// tensors.  fits: within the kernels' 32-bit tile / pixel arithmetic and 31-bit byte offsets -- the planning functions ask, the launch
+// functions write the fields into the ConvParams (set_tile_list)
+struct TileList {
+    int nt;
+    long long T;
+    unsigned y_bytes, res_bytes;
+    bool fits;
+};
+inline TileList tile_list(const ConvParams &p, int bm, int bn) {
+    TileList t;
+    const long long mt = ((long long)p.M + bm - 1) / bm, dmax = p.Wo > p.Ho ? p.Wo : p.Ho;
+    t.nt = (p.Cout + bn - 1) / bn;
+    t.T = mt * t.nt;
+    const unsigned long long yb = (((unsigned long long)p.N * p.OH * p.OW - 1) * p.out_cs + p.Cout) * 2ull;
+    const unsigned long long rb = p.res ? (((unsigned long long)p.N * p.OH * p.OW - 1) * p.res_cs + p.Cout) * 2ull : 0ull;
+    t.fits = mt * bm * dmax < 0x100000000ll && t.T * t.nt < 0x100000000ll && t.T <= 0x7fffffffll && yb < 0x7fffff00ull && rb < 0x7fffff00ull;
+    t.y_bytes = (unsigned)yb;
+    t.res_bytes = (unsigned)rb;
+    return t;
+}
+inline void set_tile_list(ConvParams &p, const TileList &t) {
+    p.nt = t.nt;
+    p.ntiles = (int)t.T;
+    p.use_magic = 1;
+    p.magic_wo = magic_u32(p.Wo);
+    p.magic_ho = magic_u32(p.Ho);
+    p.magic_nt = magic_u32(p.nt);
+    p.y_bytes = t.y_bytes;
+    p.res_bytes = t.res_bytes;
+}
+
 // blocks of `tb` threads for `total` work items, at least one and at most `cap` (the elementwise passes and the split-K reduces)
 inline int grid_for(long long total, int tb = 256, int cap = 32768) {
     long long nb = (total + tb - 1) / tb;
@@ -271,49 +320,71 @@ inline int ilog2_exact(int v) {
     return (1 << l) == v ? l : -1;
 }
 
-// conv.hip, for conv_dgrad.hip: descriptor check, the dispatch of one launch, and the switches both units read
+// conv_dispatch.hip: descriptor check; the shape part of a launch from its descriptor (tensor geometry, GEMM sizes, the regular tap window,
+// dense output placement, the epilogue) and the pixel grid of a launch (Ho x Wo per image, M = N * Ho * Wo; false: no pixels, or more than
+// the 31-bit pixel index holds); layer 0's shape and launch parameters; the plan of one launch and its execution; the switches several
+// units read
 int conv_validate(const ryolo_conv_desc *d);
-int dispatch(ConvParams &p, int ksize, int pick, const ConvLaunch &lc);
+bool conv_shape(const ryolo_conv_desc *d, ConvParams &p);
+bool conv_pixels(ConvParams &p, long long Ho, long long Wo);
+bool conv0_shape(const ryolo_conv_desc *d, int out_cs);
+bool conv0_params(const ryolo_conv_desc *d, int out_cs, ConvParams &p, int gpw, unsigned *nblk);
+bool conv0_halo_on();
+// The plan of the launch `p` describes: the forced family (pick = ryolo_conv_desc::tile's low byte) or, for pick 0, the first family in the
+// dispatch order whose planning function accepts.  want_reduce: the launch must carry the folded BatchNorm-backward reduce (stride-1 data
+// gradients, pick 0); the plan then holds the rows it writes.  kernel < 0: refused.
+ConvPlan conv_plan(const ConvParams &p, int ksize, int pick, bool want_reduce);
+int conv_launch(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc);
 long long nt_out_min_bytes();
-bool conv_pw_disabled();
-int mq128_knob();
 
-// conv_mp.hip: 256-channel x BM-pixel workgroup tile, 8 waves, multi-phase K loop (FAST path only).
-// Returns RYOLO_EINVAL when the shape does not qualify (caller falls back to the other tiles).
-int launch_conv_mp(ConvParams &p, int bm /* 256, 192, 0 = pick */, int variant, const ConvLaunch &lc);
-int conv_mp_pick_bm(const ConvParams &p);
+// Every family below: X_plan() answers whether the family serves the launch -- eligibility and every size guard -- and fills its part of
+// the plan; it writes nothing into the ConvParams.  launch_X() executes such a plan: it derives the ConvParams fields its kernel reads,
+// picks the instantiation and launches; RYOLO_ELAUNCH, or RYOLO_EINVAL for a plan that names no instantiation (an internal error).
+// conv.hip: the implicit-GEMM tiles (IGEMM_TILES), one tile per workgroup or -- short-K launches with a deep tile list -- a persistent
+// grid; no_persist / force_persist: the caller's say on that grid (tile bits 0x200 / 0x800, conv_plan()'s rules); reduce: the folded
+// BatchNorm reduce (the persistent 1x1 2x2-wave tile; the 256 x 64 / 256 x 32 tiles and the 3x3 128 x 128 tile one tile per workgroup)
+bool conv_igemm_plan(const ConvParams &p, int ksize, int tile, bool no_persist, bool force_persist, bool reduce, ConvPlan &pl);
+int launch_conv_igemm(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc);
+// ... and Darknet-53 layer 0 on conv3x3_c8_direct_kernel: pl.bm 16-pixel groups per wave, pl.grid blocks
+int launch_conv0_direct(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc);
+// conv_mp.hip: 256-channel x BM-pixel workgroup tile, 8 waves, multi-phase K loop (FAST path only); bm 256, 192 or 0 = pick per shape
 bool conv_mp_eligible(const ConvParams &p);
+int conv_mp_pick_bm(const ConvParams &p);
+bool conv_mp_plan(const ConvParams &p, int bm, int variant, ConvPlan &pl);
+int launch_conv_mp(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc);
 // conv_mq.hip: 128-pixel x 256-channel tile, 4 waves, two independent workgroups per CU (same eligibility as conv_mp)
-int launch_conv_mq(ConvParams &p, int variant, const ConvLaunch &lc);
-// ... and its 128-CHANNEL members (round 5): bm = 128 or 64 pixels per tile; C_out % 128 == 0, otherwise conv_mq's conditions.  lc.bnred
-// (stride-1 launches without statistics): the folded BatchNorm reduce, one row of part[conv_mq128_grid()][3][C] per workgroup
+bool conv_mq_plan(const ConvParams &p, int variant, ConvPlan &pl);
+int launch_conv_mq(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc);
+// ... and its 128-CHANNEL members (measurement build only): bm = 128 or 64 pixels per tile; C_out % 128 == 0, otherwise conv_mq's
+// conditions.  reduce (stride-1 launches without statistics): the folded BatchNorm reduce, one row per workgroup
 bool conv_mq128_eligible(const ConvParams &p);
-int conv_mq128_grid(const ConvParams &p, int bm);    // workgroups of the launch (= rows of BatchNorm-reduce partials), 0 = not served
-int launch_conv_mq128(ConvParams &p, int bm, const ConvLaunch &lc);
+bool conv_mq128_plan(const ConvParams &p, int bm, bool reduce, ConvPlan &pl);
+int launch_conv_mq128(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc);
 // conv_stem.hip: 3x3, C_in 32 -> C_out 64, stride 1 / 2: the input patch of an 8 x 32 output block staged once, the filter in registers
-bool conv_stem_eligible(const ConvParams &p, int ksize);
-int launch_conv_stem(ConvParams &p, const ConvLaunch &lc);
-bool conv_stem64_eligible(const ConvParams &p, int ksize);      // conv_stem.hip: 3x3 / 1, 64 -> 128
-int launch_conv_stem64(ConvParams &p, const ConvLaunch &lc);
+bool conv_stem_plan(const ConvParams &p, int ksize, ConvPlan &pl);
+int launch_conv_stem(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc);
+bool conv_stem64_plan(const ConvParams &p, int ksize, ConvPlan &pl);      // conv_stem.hip: 3x3 / 1, 64 -> 128
+int launch_conv_stem64(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc);
 // conv_stem.hip: Darknet-53 layer 0 (3x3, 8 -> 32) forward with its input patch staged in LDS (no statistics); slope_dev: optional device
 // scalar for leaky / PReLU; round_z: BatchNorm applied to z rounded to bf16 (training recompute)
 int launch_conv0_halo(ConvParams &p, const float *slope_dev, int round_z, const ConvLaunch &lc);
 // conv_stem.hip: the data gradients of the two 3x3 32 -> 64 stem layers (64 -> 32 channels in the gradient's direction) as one persistent
 // launch each -- stride 2: all four output-parity classes from one staged dz patch, w_classes = the four classic class images of
-// ryolo_conv_pack_weights_dgrad; stride 1: its single nine-tap image
-// cdz = channels of dz: 64 (layers 1 / 3) or 128 (layer 5, stride 2 only: the waves split the output channels)
-int launch_conv_stem_dgrad(int cdz, int stride, const void *dz, int dz_cs, const void *w_classes, void *dx, int dx_cs, int accumulate, int N,
-                           int H, int W, int nt_out, const ConvLaunch &lc);
+// ryolo_conv_pack_weights_dgrad; stride 1: its single nine-tap image -- and of the 3x3 / 2 64 -> 128 layer (the waves split the output
+// channels).  d: the FORWARD conv; the plan: those shapes, dz and dx within 31-bit byte offsets
+bool conv_stem_dgrad_plan(const ryolo_conv_desc *d, int dz_cs, ConvPlan &pl);
+int launch_conv_stem_dgrad(const ConvPlan &pl, const ryolo_conv_desc *d, const void *dz, int dz_cs, const void *w_classes, void *dx, int accumulate,
+                           int nt_out, const ConvLaunch &lc);
 // ... and two stem layers in one launch (inference): the 32-channel tensor between them is computed into LDS, never stored
 int conv_stem_pair_kind(const ryolo_conv_desc *first, const ryolo_conv_desc *second, int shortcut_from_input);
 int launch_conv_stem_pair(int kind, ConvParams &p /* the second layer */, const void *x, unsigned x_bytes, int in_cs, int H, int W,
                           const void *w_first, int kpad_first, const float *scale_first, const float *shift_first, int act_first,
                           float slope_first, hipStream_t stream);
 // conv_pw.hip: 1x1 stride-1 layers (and their data gradients), weight-stationary: the filter slice in registers, rows through an LDS ring
-bool conv_pw_eligible(const ConvParams &p, int ksize);
+// (reduce: the folded BatchNorm reduce, MODE 3, one row per workgroup)
+bool conv_pw_plan(const ConvParams &p, int ksize, bool reduce, ConvPlan &pl);
 bool conv_pw_preferred(const ConvParams &p);        // the shapes on which it beats the 128 x 128 tile (auto dispatch)
-int conv_pw_grid(const ConvParams &p);             // workgroups (= rows of BatchNorm-reduce partials) of the launch, 0 = not served
-int launch_conv_pw(ConvParams &p, const ConvLaunch &lc);      // lc.bnred: the folded BatchNorm reduce (MODE 3)
+int launch_conv_pw(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc);
 // a YOLO head (1x1, K = 256, na*no <= 512 channels) decoded from the accumulators: io / p rows out, no head tensor; with `head` (the
 // training forward) p rows and the bf16 head tensor [M][head_cs] out, no io rows
 bool conv_pw_decode_supported(const ConvParams &p, int na, int no);
@@ -328,7 +399,7 @@ int ryolo_mp_ablation_variant(int slot);   // conv_mp.hip: VAR code stored in de
 // launch path, no race with a setenv from another thread.  Every other environment switch of rounds 3-5 (thresholds, sweep orders, slab
 // sizes, the 128-channel conv_mq family ...) exists in the measurement build only (-DRYOLO_MP_ABLATION, abl_env()).
 enum TuneKey { TUNE_CONV3X3 = 0, TUNE_CONV1X1, TUNE_RNMS_TILES, TUNE_MQ_KORDER, TUNE_BN_REDUCE_TILES, TUNE_STEM_DGRAD, TUNE_COUNT };
-const char *tune(TuneKey k);               // conv.hip: the switch's value, nullptr = unset
+const char *tune(TuneKey k);               // conv_dispatch.hip: the switch's value, nullptr = unset
 #ifdef RYOLO_MP_ABLATION
 inline const char *abl_env(const char *name) { return getenv(name); }
 #else

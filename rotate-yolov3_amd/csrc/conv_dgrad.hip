@@ -1,6 +1,7 @@
 // rotate-yolov3_amd/csrc/conv_dgrad.hip -- the data gradient of the convolutions: the tap classes of the stride-2 layers, the weight
-// packers (classic, x-fused, batched), the plan of the folded BatchNorm-backward reduce, and the entry points that build the launches
-// and hand them to conv.hip's dispatch().
+// packers (classic, x-fused, batched), and the entry points and queries: they build each class's launch through the shape code the
+// forward uses (conv_dispatch.hip: conv_shape), plan it with conv_plan() -- the folded BatchNorm-backward reduce included -- and
+// execute the plans with conv_launch().
 #include <cstring>
 
 #include "conv_common.h"
@@ -383,222 +384,178 @@ int ryolo_conv_pack_weights_dgrad(const float *w_oihw, int Cout, int Cin, int ks
 
 }  // extern "C"
 
-// the data gradient behind ryolo_conv2d_dgrad[_bnreduce], the dry runs of ryolo_conv_dgrad_kernel_choice and of the plan below (lc.choice:
-// nothing is dereferenced before the launch sites; only whether `accumulate` is set matters)
-static int conv_dgrad(const ryolo_conv_desc *d /* the FORWARD conv */, const void *dz, int dz_cstride, const void *packed_dgrad, const float *ones,
-                      const float *zeros, void *dx, int accumulate, const ConvLaunch &lc) {
-    if (conv_validate(d) != RYOLO_OK) return RYOLO_EINVAL;
-    if (d->stride != 1 && !(d->stride == 2 && d->ksize == 3 && d->pad == 1)) return RYOLO_EINVAL;
-    if ((dz_cstride & 7) || dz_cstride < d->Cout) return RYOLO_EINVAL;
+// The launches of one data gradient and their plans: the stem kernel (one launch, conv_stem.hip), or one implicit-GEMM launch per
+// output-parity class (stride 1: one; stride 2: two x-fused or four classic; a class without pixels has none)
+struct DgradPlan {
+    bool stem = false;
+    ConvPlan stem_plan;
+    int n = 0;
+    ConvParams p[4];
+    ConvPlan pl[4];
+    int nt_out = 0;
+    // every launch has a kernel
+    bool launchable() const {
+        for (int i = 0; i < n; i++)
+            if (pl[i].kernel < 0) return false;
+        return true;
+    }
+    // the kernel the queries report: the last non-empty class's (-1: refused, or nothing to launch)
+    int kernel() const { return stem ? stem_plan.kernel : (n > 0 && launchable() ? pl[n - 1].kernel : -1); }
+};
+
+// Builds the launches of the data gradient of `d` (the FORWARD conv) behind ryolo_conv2d_dgrad[_bnreduce] and the queries; false: the
+// descriptor is refused.  Each class is a convolution of dz in the gradient's direction -- C_out -> C_in channels, stride 1 -- whose
+// ConvParams come from conv_shape() like the forward's; the class then gets its tap list, filter image, pixel grid and output placement.
+// (The queries pass stand-ins for the pointers and a dense dz: the plans depend only on whether `accumulate` is set.)
+static bool dgrad_plan(const ryolo_conv_desc *d, const void *dz, int dz_cstride, const void *packed_dgrad, const float *ones, const float *zeros,
+                       void *dx, int accumulate, bool want_reduce, DgradPlan &out) {
+    if (conv_validate(d) != RYOLO_OK) return false;
+    if (d->stride != 1 && !(d->stride == 2 && d->ksize == 3 && d->pad == 1)) return false;
+    if ((dz_cstride & 7) || dz_cstride < d->Cout || (want_reduce && d->stride != 1)) return false;
+    if ((long long)d->N * d->H * d->W > 0x7fffffffLL - 512) return false;      // dx is indexed by pixel, like every launch's output (conv_pixels)
     const int Ho = (d->H + 2 * d->pad - d->ksize) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->ksize) / d->stride + 1;
     const int rows = (d->Cin + 127) / 128 * 128;
     const unsigned long long dz_pix = (unsigned long long)d->N * Ho * Wo;
-    const int nt_out = (long long)d->N * d->H * d->W * d->Cin * 2 >= nt_out_min_bytes() ? 1 : 0;
+    out.nt_out = (long long)d->N * d->H * d->W * d->Cin * 2 >= nt_out_min_bytes() ? 1 : 0;
     const char *wsrc = (const char *)packed_dgrad;
     // x-fused stride-2 classes when the input gradient is dense and its rows hold an even number of pixels (tile bit 0x8000
     // forces the four classic classes: tests / A-B)
     const bool xfuse = dgrad_xfusable(d->Cin, d->ksize, d->stride) && d->pad == 1 && (d->W & 1) == 0 &&
                        d->in_cstride == d->Cin && !(d->tile & 0x8000);
     if (xfuse) wsrc += dgrad_classic_bytes(d->Cout, d->Cin, d->ksize, d->stride);
-    // Darknet-53 layers 1 and 3 (3x3, 32 -> 64, stride 2 / 1): one persistent launch with the dz patch staged once and the filter in
-    // registers (conv_stem.hip); tile bit 0x8000 (the classic classes) and RYOLO_STEM_DGRAD=0 keep the implicit-GEMM launches (tests, A/B)
+    // Darknet-53 layers 1 and 3 (3x3, 32 -> 64, stride 2 / 1) and 5 (3x3 / 2, 64 -> 128): one persistent launch with the dz patch staged
+    // once and the filter in registers (conv_stem.hip); tile bit 0x8000 (the classic classes), a forced tile and RYOLO_STEM_DGRAD (bit 0:
+    // the 64 -> 32 kernels, bit 1: the 128 -> 64 one; A/B, ryolo_set_tuning) keep the implicit-GEMM launches, which also serve what its
+    // plan refuses (dz of 2 GiB and more: they did before this kernel existed)
     // (the stride-1 64 -> 128 layers keep the 256 x 64 tile: it carries the folded BatchNorm reduce, and the channel-split kernel measured
     // 286 us against its 278 / 332 with the reduce -- step 48.50 vs 48.44 ms)
-    if (!lc.bnred && d->ksize == 3 && d->pad == 1 && ((d->Cin == 32 && d->Cout == 64) || (d->Cin == 64 && d->Cout == 128 && d->stride == 2)) &&
-        !(d->tile & 0x80ff)) {
+    if (!want_reduce && !(d->tile & 0x80ff)) {
         const char *e = tune(TUNE_STEM_DGRAD);
-        const int knob = e ? atoi(e) : 3;              // bit 0: the 64 -> 32 kernels, bit 1: the 128 -> 64 one (A/B; ryolo_set_tuning)
-        if (knob & (d->Cout == 64 ? 1 : 2)) {
-            // (its size guards -- dz of 2 GiB and more, tile counts beyond 2^31 -- answer EINVAL before anything is enqueued: those launches
-            // fall through to the parity-class launches below, which served them before this kernel existed)
-            if (buffer_extent(dz_pix, dz_cstride, d->Cout) && buffer_extent((unsigned long long)d->N * d->H * d->W, d->in_cstride, d->Cin)) {
-                RYOLO_CONV_DRY_RUN(lc, RYOLO_CONV_KERNEL_STEM_DGRAD);
-                const int rc = launch_conv_stem_dgrad(d->Cout, d->stride, dz, dz_cstride, packed_dgrad, dx, d->in_cstride, accumulate, d->N, d->H,
-                                                      d->W, nt_out, lc);
-                if (rc != RYOLO_EINVAL) return rc;
-            }
+        const int knob = e ? atoi(e) : 3;
+        if ((knob & (d->Cout == 64 ? 1 : 2)) && conv_stem_dgrad_plan(d, dz_cstride, out.stem_plan)) {
+            out.stem = true;
+            return true;
         }
     }
+    ryolo_conv_desc g = *d;      // the gradient's direction: dz -> dx
+    g.H = Ho; g.W = Wo; g.Cin = d->Cout; g.in_cstride = dz_cstride;
+    g.Cout = d->Cin; g.out_cstride = d->in_cstride; g.res_cstride = d->in_cstride;
+    g.stride = 1; g.pad = d->ksize - 1 - d->pad;
+    g.act = RYOLO_ACT_LINEAR; g.slope = 0.f; g.upsample = 1;
     const int ncls = d->stride == 1 ? 1 : (xfuse ? 2 : 4);
     const int wrows = xfuse ? (2 * d->Cin + 127) / 128 * 128 : rows;
     for (int cls = 0; cls < ncls; cls++) {
         int dy[9], dxx[9], khs[9], kws[9];
         const int nt = xfuse ? dgrad_xfused_class(cls, dy, dxx, khs, kws, kws)
                              : dgrad_classes(d->ksize, d->stride, d->pad, cls, dy, dxx, khs, kws);
-        ConvParams p{};
+        ConvParams &p = out.p[out.n];
+        p = ConvParams{};
+        if (!conv_shape(&g, p)) return false;
         p.x = (const __bf16 *)dz;
         p.w = (const __bf16 *)wsrc;
         p.scale = ones; p.shift = zeros;
-        p.res = accumulate ? (const __bf16 *)dx : nullptr;
+        // (the folded reduce is planned for the accumulating form whatever `accumulate` says, as its rows query plans it: a launch that
+        // only stores stays within every guard of the one that also reads dx)
+        p.res = accumulate || want_reduce ? (const __bf16 *)dx : nullptr;
         p.y = (__bf16 *)dx;
-        p.N = d->N; p.H = Ho; p.W = Wo; p.Cin = d->Cout; p.in_cs = dz_cstride;
-        p.Cout = d->Cin; p.out_cs = d->in_cstride; p.res_cs = d->in_cstride;
         p.K = nt * d->Cout;
         p.Kpad = (p.K + BK - 1) / BK * BK;
-        p.act = RYOLO_ACT_LINEAR; p.ups = 1;
         p.cin_log2 = ilog2_exact(d->Cout);
         p.ntaps = nt;
-        for (int t = 0; t < nt; t++) { p.tap_dy[t] = dy[t]; p.tap_dx[t] = dxx[t]; }
-        p.stride = 1; p.OH = d->H;
-        if (d->stride == 1) {
-            p.pad = d->ksize - 1 - d->pad;
-            p.Ho = d->H; p.Wo = d->W;
-            p.os = 1; p.osx = 1; p.OW = d->W;
-        } else if (xfuse) {
-            p.Cout = 2 * d->Cin; p.out_cs = 2 * d->in_cstride; p.res_cs = 2 * d->in_cstride;
-            p.Ho = (d->H - cls + 1) / 2; p.Wo = d->W / 2;                 // rows of parity `cls` x pixel PAIRS
-            p.os = 2; p.osx = 1; p.ooy = cls; p.OW = d->W / 2;
-        } else {
-            const int a = cls >> 1, b = cls & 1;
-            p.Ho = (d->H - a + 1) / 2; p.Wo = (d->W - b + 1) / 2;      // grid of input pixels with this parity
-            p.os = 2; p.osx = 2; p.ooy = a; p.oox = b; p.OW = d->W;
+        for (int t = 0; t < 9; t++) { p.tap_dy[t] = t < nt ? dy[t] : 0; p.tap_dx[t] = t < nt ? dxx[t] : 0; }
+        wsrc += ((size_t)wrows * p.Kpad + 128) * 2;
+        if (d->stride == 2) {
+            // the class's grid of input pixels, placed with step 2 in dx; its taps carry their own offsets (no padding)
+            const int a = xfuse ? cls : cls >> 1, b = cls & 1;
+            p.pad = 0;
+            p.OH = d->H;
+            p.os = 2; p.ooy = a;
+            if (xfuse) {      // rows of parity `cls` x pixel PAIRS
+                p.Cout = 2 * d->Cin; p.out_cs = 2 * d->in_cstride; p.res_cs = 2 * d->in_cstride;
+                p.osx = 1; p.OW = d->W / 2;
+                if ((d->H - a + 1) / 2 <= 0 || d->W / 2 <= 0) continue;
+                if (!conv_pixels(p, (d->H - a + 1) / 2, d->W / 2)) return false;
+            } else {
+                p.osx = 2; p.oox = b; p.OW = d->W;
+                if ((d->H - a + 1) / 2 <= 0 || (d->W - b + 1) / 2 <= 0) continue;
+                if (!conv_pixels(p, (d->H - a + 1) / 2, (d->W - b + 1) / 2)) return false;
+            }
         }
-        const size_t wbytes = ((size_t)wrows * p.Kpad + 128) * 2;
-        wsrc += wbytes;
-        if (p.Ho <= 0 || p.Wo <= 0) continue;
-        p.M = (int)((long long)d->N * p.Ho * p.Wo);
         p.fast = (d->Cout % BK == 0) && buffer_extent(dz_pix, dz_cstride, d->Cout, &p.x_bytes) && buffer_extent(wrows, p.Kpad, p.Kpad + 128, &p.w_bytes);
         if (!p.fast) p.x_bytes = p.w_bytes = 0;
-        if (!p.fast && (d->stride != 1 || (d->ksize == 3 && p.cin_log2 < 0))) return RYOLO_EINVAL;
+        if (!p.fast && (d->stride != 1 || (d->ksize == 3 && p.cin_log2 < 0))) return false;
         p.no_persist = (d->tile & 0x200) ? 1 : 0;
         p.pw_grid_cap = (d->tile & 0xff) == 13 ? (d->tile >> 16) & 0xff : 0;
-        p.nt_out = nt_out;
-        const int pick = (d->tile & 0xff);   // 0 = auto
-        const int rc = dispatch(p, d->ksize, pick, lc);
+        p.nt_out = out.nt_out;
+        out.pl[out.n] = conv_plan(p, d->ksize, d->tile & 0xff, want_reduce);
+        if (!accumulate) p.res = nullptr;
+        out.n++;
+    }
+    return true;
+}
+
+static int dgrad_launch(DgradPlan &dp, const ryolo_conv_desc *d, const void *dz, int dz_cstride, const void *packed_dgrad, void *dx, int accumulate,
+                        const ConvLaunch &lc) {
+    if (dp.stem) return launch_conv_stem_dgrad(dp.stem_plan, d, dz, dz_cstride, packed_dgrad, dx, accumulate, dp.nt_out, lc);
+    if (!dp.launchable()) return RYOLO_EINVAL;
+    for (int i = 0; i < dp.n; i++) {
+        const int rc = conv_launch(dp.pl[i], dp.p[i], lc);
         if (rc != RYOLO_OK) return rc;
     }
     return RYOLO_OK;
 }
 
-// the kernel the accumulating data gradient of `d` takes (dry run), -1 when it is refused; bnred + mode: with the folded reduce
-static int dgrad_choice(const ryolo_conv_desc *d, const BnRed *bnred = nullptr, int mode = 0) {
-    int choice = -1;
-    ConvLaunch lc;
-    lc.bnred = bnred; lc.bnred_mode = mode; lc.choice = &choice;
-    void *fake = (void *)(uintptr_t)4096;      // never dereferenced: the dispatch returns before any launch
-    return conv_dgrad(d, fake, d ? d->Cout : 0, fake, (const float *)fake, (const float *)fake, fake, 1, lc) == RYOLO_OK ? choice : -1;
-}
-
-// ---- which kernel carries the BatchNorm-backward reduce of a block whose final dy this data gradient stores, and how many rows of partial
-// sums (= workgroups of a persistent launch, pixel tiles of a one-tile-per-workgroup launch) that launch writes; 0 = it cannot.
-// Mode 3: the stride-1 data gradients whose natural kernel is one of the one-tile-per-workgroup / narrow tiles (the 3x3 layers with
-// C_in <= 128, the 1x1 layers with C_in <= 64).  Two dry runs of the dispatch decide: the kernel the plain data gradient takes must be one
-// of those tiles (a layer that conv_mq / conv_mp serve keeps them: the reduce is not worth a slower conv), and the launch with the reduce
-// must exist.  Returns the rows (= pixel tiles) or 0.
-static int bnreduce_plan_tiles(const ryolo_conv_desc *d) {
-    if (d->stride != 1 || (d->tile & 0xff) || d->in_cstride != d->Cin || (d->Cin & 7)) return 0;
-    int knob = 1;
-    {   // RYOLO_BN_REDUCE_TILES = 0: off (A/B timing; ryolo_set_tuning)
-        const char *e = tune(TUNE_BN_REDUCE_TILES);
-        if (e) knob = atoi(e);
-        if (knob == 0) return 0;
-    }
-    const BnRed br{};
-    const int natural = dgrad_choice(d), fused = natural < 0 ? -1 : dgrad_choice(d, &br, 3);
-    if (fused < 0 || natural != fused) return 0;
-    const int tile = fused - RYOLO_CONV_KERNEL_IGEMM;
-    const int bm = tile == 1 ? 128 : ((tile == 2 || tile == 3) ? 256 : 0);
-    if (!bm) return 0;
-    if (tile == 3) return 0;           // 256 x 32: the plain data gradient runs on the persistent grid (short K), 233 us faster than this launch
-    if (tile == 1 && knob == 2) return 0;
-    const long long M = (long long)d->N * d->H * d->W;
-    return (int)((M + bm - 1) / bm);
-}
-
-// mode 4: the data gradient's natural kernel is one of conv_mq.hip's 128-channel tiles -- the reduce rides in its epilogue, one row per
-// workgroup.  Returns the rows (= workgroups of that launch) or 0.
-static int bnreduce_plan_mq128(const ryolo_conv_desc *d) {
-    if (d->stride != 1 || (d->tile & 0xff) || d->in_cstride != d->Cin || (d->Cin & 127) || mq128_knob() <= 0) return 0;
-    const int natural = dgrad_choice(d);
-    if (natural != RYOLO_CONV_KERNEL_MQ128 && natural != RYOLO_CONV_KERNEL_MQ64) return 0;
-    ConvParams q{};
-    q.M = (int)((long long)d->N * d->H * d->W);
-    q.Cout = d->Cin;
-    return conv_mq128_grid(q, natural == RYOLO_CONV_KERNEL_MQ128 ? 128 : 64);
-}
-
-// Modes 1 / 2 (1x1 layers with whole 128-channel tiles): conv_pw.hip where it is the faster data gradient (K = 128: the 76^2 residual
-// blocks, 127 vs 133 us at bs 64) and where the persistent 128 x 128 tile does not apply (tile lists less than 2.5 rounds deep: 19^2); the
-// persistent tile elsewhere (38^2: 68 vs 70 us, 19^2 K 512: 49 vs 54 us; tools/pw_bench.py --train).  persist_grid() is the test
-// dispatch() / launch_variant() apply, so the rows returned are the grid launched.
-static int bnreduce_plan(const ryolo_conv_desc *d, int *mode) {
-    *mode = 0;
-    if (conv_validate(d) != RYOLO_OK) return 0;
-    {
-        const int r = bnreduce_plan_mq128(d);
-        if (r > 0) {
-            *mode = 4;
-            return r;
-        }
-    }
-    auto tiles = [&]() {
-        const int r = bnreduce_plan_tiles(d);
-        if (r > 0) *mode = 3;
-        return r;
-    };
-    if (d->ksize != 1 || d->stride != 1 || d->pad != 0) return tiles();
-    if ((d->Cin & 127) || (d->Cout & 63) || (d->tile & 0xff)) return tiles();
-    const long long M = (long long)d->N * d->H * d->W;
-    int g_pw = 0;
-    {   // the data gradient as conv_pw.hip sees it (K = the forward's C_out, channels = its C_in): its grid when it serves the shape
-        ConvParams q{};
-        q.Cin = d->Cout; q.Kpad = (d->Cout + BK - 1) / BK * BK; q.Cout = d->Cin;
-        const int g = conv_pw_disabled() ? 0 : conv_pw_grid(q);
-        if (g > 0 && d->in_cstride == d->Cin && buffer_extent(M + 1024 * 128, d->Cout, d->Cout) && buffer_extent(M, d->Cin, d->Cin)) g_pw = g;
-    }
-    const PersistGrid pg = persist_grid(M, 128, d->Cin, 128, d->H, d->W);
-    const bool persist_ok = pg.deep && pg.exact && buffer_extent(M, d->Cout, d->Cout);
-    if (g_pw > 0 && (d->Cout == 128 || !persist_ok)) {
-        *mode = 1;
-        return g_pw;
-    }
-    if (persist_ok) {
-        *mode = 2;
-        return pg.grid;
-    }
-    return tiles();
+// the plan the queries read: the accumulating data gradient of `d` over a dense dz
+static bool dgrad_query(const ryolo_conv_desc *d, bool want_reduce, DgradPlan &dp) {
+    void *fake = (void *)(uintptr_t)4096;      // never dereferenced: nothing is launched
+    return d && dgrad_plan(d, fake, d->Cout, fake, (const float *)fake, (const float *)fake, fake, 1, want_reduce, dp);
 }
 
 extern "C" {
 
 // rows of partial sums the fused launch writes (= workgroups of a persistent launch, pixel tiles of a one-tile-per-workgroup launch), 0 when
-// this conv's data gradient cannot carry the reduce: stride 1, dense input gradient, and one of the kernels with the folded pass (the
-// persistent 2x2 tile / conv_pw.hip for 1x1 layers with whole 128-channel tiles, the narrow and the 128 x 128 one-tile kernels otherwise)
+// this conv's data gradient cannot carry the reduce: stride 1, and one of the kernels with the folded pass (conv_plan(): the persistent
+// 2x2 tile / conv_pw.hip for 1x1 layers with whole 128-channel tiles, the narrow and the 128 x 128 one-tile kernels otherwise)
 int ryolo_conv2d_dgrad_bnreduce_rows(const ryolo_conv_desc *d) {
-    int mode;
-    return bnreduce_plan(d, &mode);
+    DgradPlan dp;
+    return dgrad_query(d, true, dp) && dp.n == 1 ? dp.pl[0].rows : 0;
 }
 
 int ryolo_conv2d_dgrad(const ryolo_conv_desc *d /* the FORWARD conv */, const void *dz, int dz_cstride,
                        const void *packed_dgrad, const float *ones, const float *zeros, void *dx, int accumulate,
                        void *stream_) {
     if (!dz || !packed_dgrad || !ones || !zeros || !dx) return RYOLO_EINVAL;
+    DgradPlan dp;
+    if (!dgrad_plan(d, dz, dz_cstride, packed_dgrad, ones, zeros, dx, accumulate, false, dp)) return RYOLO_EINVAL;
     ConvLaunch lc;
     lc.stream = (hipStream_t)stream_;
-    return conv_dgrad(d, dz, dz_cstride, packed_dgrad, ones, zeros, dx, accumulate, lc);
+    return dgrad_launch(dp, d, dz, dz_cstride, packed_dgrad, dx, accumulate, lc);
 }
 
 int ryolo_conv2d_dgrad_bnreduce(const ryolo_conv_desc *d, const void *dz, int dz_cstride, const void *packed_dgrad, const float *ones,
                                 const float *zeros, void *dx, int accumulate, const void *z, int z_cstride, const float *scale,
                                 const float *shift, const float *mean, const float *invstd, const float *slope, float *part,
                                 void *stream_) {
-    ConvLaunch lc;
-    if (!bnreduce_plan(d, &lc.bnred_mode) || !z || (z_cstride & 7) || z_cstride < d->Cin || !scale || !shift || !mean || !invstd ||
-        !slope || !part || d->in_cstride != d->Cin || !dz || !packed_dgrad || !ones || !zeros || !dx)
+    if (!d || !z || (z_cstride & 7) || z_cstride < d->Cin || !scale || !shift || !mean || !invstd || !slope || !part || d->in_cstride != d->Cin ||
+        !dz || !packed_dgrad || !ones || !zeros || !dx)
         return RYOLO_EINVAL;
+    DgradPlan dp, asked;
+    if (!dgrad_plan(d, dz, dz_cstride, packed_dgrad, ones, zeros, dx, accumulate, true, dp) || dp.n != 1 || dp.pl[0].kernel < 0 || dp.pl[0].rows <= 0)
+        return RYOLO_EINVAL;
+    // the caller sized `part` by ryolo_conv2d_dgrad_bnreduce_rows(), which plans a dense dz: a strided one must come to the same rows
+    if (dz_cstride != d->Cout && (!dgrad_query(d, true, asked) || asked.n != 1 || asked.pl[0].rows != dp.pl[0].rows)) return RYOLO_EINVAL;
     BnRed br;
     br.z = (const __bf16 *)z; br.z_cs = z_cstride; br.scale = scale; br.shift = shift; br.mean = mean; br.invstd = invstd;
     br.slope = slope; br.part = part;
+    ConvLaunch lc;
     lc.bnred = &br;
     lc.stream = (hipStream_t)stream_;
-    return conv_dgrad(d, dz, dz_cstride, packed_dgrad, ones, zeros, dx, accumulate, lc);
+    return dgrad_launch(dp, d, dz, dz_cstride, packed_dgrad, dx, accumulate, lc);
 }
 
 int ryolo_conv_dgrad_kernel_choice(const ryolo_conv_desc *d, int with_bn_reduce) {
-    if (!with_bn_reduce) return dgrad_choice(d);
-    const BnRed br{};
-    int mode = 0;
-    return bnreduce_plan(d, &mode) ? dgrad_choice(d, &br, mode) : -1;      // ryolo_conv2d_dgrad_bnreduce: the kernel its plan picks
+    DgradPlan dp;
+    return dgrad_query(d, with_bn_reduce != 0, dp) ? dp.kernel() : -1;
 }
 
 }  // extern "C"

@@ -606,43 +606,41 @@ __global__ void __launch_bounds__(512) conv_mp_kernel(const ConvParams p) {
     }
 }
 
-inline unsigned mp_magic_u32(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
-
 void *g_trace_buf = nullptr;
 int g_dbg[4] = {0, 0, 0, 0};
 int g_var[16] = {0};
 
 template <int BM, int GEN, int VAR, int KO = 0>
-int mp_launch(ConvParams &p, const ConvLaunch &lc) {
+int mp_launch(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc) {
     if (VAR & (128 | 1024)) p.stat_part = (double *)g_trace_buf;
     constexpr int LDS = GEN == 1 ? MP_LDS_GEN : MP_LDS;
-    const int mt = (p.M + BM - 1) / BM;
-    p.nt = (p.Cout + MP_BN - 1) / MP_BN;
-    const long long T = (long long)mt * p.nt;
-    const long long dmax = p.Wo > p.Ho ? p.Wo : p.Ho, mpad = (long long)mt * BM;
-    if (mpad * dmax >= 0x100000000ll || T * p.nt >= 0x100000000ll || T > 0x7fffffffll) return RYOLO_EINVAL;
-    p.use_magic = 1;
-    p.magic_wo = mp_magic_u32(p.Wo);
-    p.magic_ho = mp_magic_u32(p.Ho);
-    p.magic_nt = mp_magic_u32(p.nt);
-    p.ntiles = (int)T;
-    {
-        const unsigned long long yb = (((unsigned long long)p.N * p.OH * p.OW - 1) * p.out_cs + p.Cout) * 2ull;
-        const unsigned long long rb = p.res ? (((unsigned long long)p.N * p.OH * p.OW - 1) * p.res_cs + p.Cout) * 2ull : 0ull;
-        if (yb >= 0x7fffff00ull || rb >= 0x7fffff00ull) return RYOLO_EINVAL;
-        p.y_bytes = (unsigned)yb;
-        p.res_bytes = (unsigned)rb;
-    }
-    RYOLO_CONV_DRY_RUN(lc, BM == 192 ? RYOLO_CONV_KERNEL_MP192 : RYOLO_CONV_KERNEL_MP256);
-    int cus = cu_count() & ~7;
-    if (g_dbg[1] >= 8) cus = g_dbg[1] & ~7;   // ablation builds: cap on the persistent grid (0 in the product)
-    const int grid = T >= cus ? cus : (int)((T + 7) & ~7ll);   // a multiple of 8 (XCD chunking); surplus workgroups exit at once
-    return launch_kernel<conv_mp_kernel<BM, GEN, VAR, KO>>(dim3((unsigned)grid), dim3(512), LDS, lc.stream, p);
+    set_tile_list(p, tile_list(p, BM, MP_BN));
+    return launch_kernel<conv_mp_kernel<BM, GEN, VAR, KO>>(dim3((unsigned)pl.grid), dim3(512), LDS, lc.stream, p);
 }
 
 }  // namespace
 
 namespace ryolo_detail {
+
+bool conv_mp_plan(const ConvParams &p, int bm, int variant, ConvPlan &pl) {
+    if (!conv_mp_eligible(p)) return false;
+    if (bm == 0) bm = conv_mp_pick_bm(p);
+    if (bm != 256 && bm != 192) return false;
+#ifdef RYOLO_MP_ABLATION
+    if (variant != 0 && (p.stat_part != nullptr || p.os != 1)) return false;
+#else
+    if (variant != 0) return false;
+#endif
+    const TileList t = tile_list(p, bm, MP_BN);
+    if (!t.fits) return false;
+    int cus = cu_count() & ~7;
+    if (g_dbg[1] >= 8) cus = g_dbg[1] & ~7;   // ablation builds: cap on the persistent grid (0 in the product)
+    pl.kernel = bm == 192 ? RYOLO_CONV_KERNEL_MP192 : RYOLO_CONV_KERNEL_MP256;
+    pl.bm = bm;
+    pl.variant = variant;
+    pl.grid = t.T >= cus ? cus : (int)((t.T + 7) & ~7ll);   // a multiple of 8 (XCD chunking); surplus workgroups exit at once
+    return true;
+}
 
 bool conv_mp_eligible(const ConvParams &p) {
     return p.fast && !p.taps2 && p.ups == 1 && !(p.stat_part && (p.res || p.os != 1)) && (p.Cin % BK) == 0 && (p.Cout % MP_BN) == 0 && p.Kpad >= 2 * BK && p.ntaps >= 1 && p.ntaps <= 9 &&
@@ -661,24 +659,21 @@ int conv_mp_pick_bm(const ConvParams &p) {
     return (int)best_bm;
 }
 
-int launch_conv_mp(ConvParams &p, int bm, int variant, const ConvLaunch &lc) {
-    if (!conv_mp_eligible(p)) return RYOLO_EINVAL;
+int launch_conv_mp(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc) {
     const int gen = p.stat_part != nullptr ? 1 : (p.os != 1 ? 2 : 0);
-    if (bm == 0) bm = conv_mp_pick_bm(p);
-    if (bm != 256 && bm != 192) return RYOLO_EINVAL;
+    const int bm = pl.bm;
 #ifdef RYOLO_MP_ABLATION
     // schedule variants and timing-only ablations (several of them produce WRONG results): never in the shipped library
-    if (gen == 0 && variant != 0) {
+    if (pl.variant != 0) {
         p.dbg0 = g_dbg[0];
-#define MP_VAR(V) case V: return bm == 256 ? mp_launch<256, 0, V>(p, lc) : mp_launch<192, 0, V>(p, lc);
-        switch (variant) {
+#define MP_VAR(V) case V: return bm == 256 ? mp_launch<256, 0, V>(pl, p, lc) : mp_launch<192, 0, V>(pl, p, lc);
+        switch (pl.variant) {
             MP_VAR(1) MP_VAR(2) MP_VAR(8) MP_VAR(16) MP_VAR(32) MP_VAR(40) MP_VAR(64) MP_VAR(512) MP_VAR(144) MP_VAR(1024) MP_VAR(1056) MP_VAR(1032)
             default: return RYOLO_EINVAL;
         }
 #undef MP_VAR
     }
 #endif
-    if (variant != 0) return RYOLO_EINVAL;
     // K-tile order: conv_mq.hip's rule (channel-slice-major for 3x3 launches with C_in >= 512; RYOLO_MQ_KORDER = 0 | 1 forces one)
     bool cm = p.ntaps > 1 && p.Cin >= 512;
     {
@@ -688,13 +683,13 @@ int launch_conv_mp(ConvParams &p, int bm, int variant, const ConvLaunch &lc) {
         if (m && !e) cm = p.ntaps > 1 && p.Cin >= atoi(m);
     }
     if (bm == 256) {
-        if (gen == 1) return cm ? mp_launch<256, 1, 0, 1>(p, lc) : mp_launch<256, 1, 0>(p, lc);
-        if (gen == 2) return cm ? mp_launch<256, 2, 0, 1>(p, lc) : mp_launch<256, 2, 0>(p, lc);
-        return cm ? mp_launch<256, 0, 0, 1>(p, lc) : mp_launch<256, 0, 0>(p, lc);
+        if (gen == 1) return cm ? mp_launch<256, 1, 0, 1>(pl, p, lc) : mp_launch<256, 1, 0>(pl, p, lc);
+        if (gen == 2) return cm ? mp_launch<256, 2, 0, 1>(pl, p, lc) : mp_launch<256, 2, 0>(pl, p, lc);
+        return cm ? mp_launch<256, 0, 0, 1>(pl, p, lc) : mp_launch<256, 0, 0>(pl, p, lc);
     }
-    if (gen == 1) return cm ? mp_launch<192, 1, 0, 1>(p, lc) : mp_launch<192, 1, 0>(p, lc);
-    if (gen == 2) return cm ? mp_launch<192, 2, 0, 1>(p, lc) : mp_launch<192, 2, 0>(p, lc);
-    return cm ? mp_launch<192, 0, 0, 1>(p, lc) : mp_launch<192, 0, 0>(p, lc);
+    if (gen == 1) return cm ? mp_launch<192, 1, 0, 1>(pl, p, lc) : mp_launch<192, 1, 0>(pl, p, lc);
+    if (gen == 2) return cm ? mp_launch<192, 2, 0, 1>(pl, p, lc) : mp_launch<192, 2, 0>(pl, p, lc);
+    return cm ? mp_launch<192, 0, 0, 1>(pl, p, lc) : mp_launch<192, 0, 0>(pl, p, lc);
 }
 
 }  // namespace ryolo_detail

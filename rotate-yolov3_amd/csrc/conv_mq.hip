@@ -36,8 +36,8 @@
 // deep).  Per K tile a wave then stages CW/16 weight pieces in two halves and PF/4 activation pieces per half, and the counted
 // waits follow: phase 0 leaves the PF/4 pieces of XA(t+2) in flight, phase 3 the CW/16 pieces of WB(t+1).  The 128-channel
 // tile holds 48 KiB of operands (2 x 16 + 16), its accumulators 64 registers -- which leaves room for the FOLDED BATCHNORM
-// REDUCE (BNRED, stride-1 data gradients that store the final gradient of a BatchNorm block's output: conv_dgrad.hip bnreduce_plan
-// mode 4): the epilogue reads the block's z next to the running gradient, forms g = dy * act'(z * scale + shift) on the values
+// REDUCE (BNRED, stride-1 data gradients that store the final gradient of a BatchNorm block's output: conv_dispatch.hip conv_plan()
+// with want_reduce): the epilogue reads the block's z next to the running gradient, forms g = dy * act'(z * scale + shift) on the values
 // it stores and adds the 16-lane row sums of g, g * (z - mean), dy * min(u, 0) to wave-private LDS accumulators per channel
 // tile; every workgroup stores (not adds) its row of part[grid][3][C] at the end, in fixed order.
 #include <cstdlib>
@@ -682,8 +682,6 @@ __global__ void __launch_bounds__(256, 2) conv_mq_kernel(const ConvParams p, con
     }
 }
 
-inline unsigned mq_magic_u32(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
-
 #ifdef RYOLO_MP_ABLATION
 void *g_q_trace_buf = nullptr;
 int g_q_dbg[4] = {0, 0, 0, 0};
@@ -699,78 +697,72 @@ inline int mq_grid_for(long long T, int cw = 64) {
         const int v = e ? atoi(e) : 2;
         if (v >= 1 && v <= 4) per_cu = v;
     }
-    const int wgs = per_cu * (cu_count() & ~7);
+    int wgs = per_cu * (cu_count() & ~7);
+#ifdef RYOLO_MP_ABLATION
+    if (g_q_dbg[1] >= 8) wgs = g_q_dbg[1] & ~7;      // (debug cap on the persistent grid)
+#endif
     return T >= wgs ? wgs : (int)((T + 7) & ~7ll);
 }
 
 template <int GEN, int VAR, int CW = 64, int PF = 8, bool BNRED = false, int FS = 1, int KO = 0>
-int mq_launch(ConvParams &p, const ConvLaunch &lc) {
+int mq_launch(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc) {
     using L = QL<CW, PF>;
 #ifdef RYOLO_MP_ABLATION
     if (VAR & 1024) p.stat_part = (double *)g_q_trace_buf;
     p.dbg0 = g_q_dbg[0];
 #endif
     constexpr int LDS = GEN == 1 ? L::LDS_GEN : (BNRED ? L::LDS_RED : L::LDS);
-    const int mt = (p.M + L::BM - 1) / L::BM;
-    p.nt = (p.Cout + L::BN - 1) / L::BN;
-    const long long T = (long long)mt * p.nt;
-    const long long dmax = p.Wo > p.Ho ? p.Wo : p.Ho, mpad = (long long)mt * L::BM;
-    if (mpad * dmax >= 0x100000000ll || T * p.nt >= 0x100000000ll || T > 0x7fffffffll) return RYOLO_EINVAL;
-    p.use_magic = 1;
-    p.magic_wo = mq_magic_u32(p.Wo);
-    p.magic_ho = mq_magic_u32(p.Ho);
-    p.magic_nt = mq_magic_u32(p.nt);
-    p.ntiles = (int)T;
-    {
-        const unsigned long long yb = (((unsigned long long)p.N * p.OH * p.OW - 1) * p.out_cs + p.Cout) * 2ull;
-        const unsigned long long rb = p.res ? (((unsigned long long)p.N * p.OH * p.OW - 1) * p.res_cs + p.Cout) * 2ull : 0ull;
-        if (yb >= 0x7fffff00ull || rb >= 0x7fffff00ull) return RYOLO_EINVAL;
-        p.y_bytes = (unsigned)yb;
-        p.res_bytes = (unsigned)rb;
-    }
+    set_tile_list(p, tile_list(p, L::BM, L::BN));
     BnRed br = BnRed();
     if constexpr (BNRED) {
-        if (!lc.bnred || p.nt > L::STAT_NT || (p.Cout % L::BN) != 0) return RYOLO_EINVAL;
+        // z is read through a buffer descriptor; its stride is an argument of the launch, not of the plan: beyond 31-bit offsets is the
+        // caller's invalid argument
+        if (!lc.bnred || !buffer_extent(p.M, lc.bnred->z_cs, p.Cout, &br.z_bytes)) return RYOLO_EINVAL;
+        const unsigned zb = br.z_bytes;
         br = *lc.bnred;
-        const unsigned long long zb = (((unsigned long long)p.M - 1) * br.z_cs + p.Cout) * 2ull;
-        if (zb >= 0x7fffff00ull) return RYOLO_EINVAL;
-        br.z_bytes = (unsigned)zb;
+        br.z_bytes = zb;
     }
     {
         bool reg = p.ntaps == 9;
-        for (int t = 0; t < 9 && reg; t++) reg = p.tap_dy[t] == t / 3 && p.tap_dx[t] == t % 3;
+        for (int t9 = 0; t9 < 9 && reg; t9++) reg = p.tap_dy[t9] == t9 / 3 && p.tap_dx[t9] == t9 % 3;
         p.reg3 = reg ? 1 : 0;
     }
     p.korder = KO;
-    RYOLO_CONV_DRY_RUN(lc, (CW == 64 ? RYOLO_CONV_KERNEL_MQ : (PF == 8 ? RYOLO_CONV_KERNEL_MQ128 : RYOLO_CONV_KERNEL_MQ64)));
-    int grid = mq_grid_for(T, CW);
-#ifdef RYOLO_MP_ABLATION
-    if (g_q_dbg[1] >= 8) {
-        const int wgs = g_q_dbg[1] & ~7;
-        grid = T >= wgs ? wgs : (int)((T + 7) & ~7ll);
-    }
-#endif
-    return launch_kernel<conv_mq_kernel<GEN, VAR, CW, PF, BNRED, FS, KO>>(dim3((unsigned)grid), dim3(256), LDS, lc.stream, p, br);
+    return launch_kernel<conv_mq_kernel<GEN, VAR, CW, PF, BNRED, FS, KO>>(dim3((unsigned)pl.grid), dim3(256), LDS, lc.stream, p, br);
 }
 
 }  // namespace
 
 namespace ryolo_detail {
 
-int launch_conv_mq(ConvParams &p, int variant, const ConvLaunch &lc) {
-    if (!conv_mp_eligible(p)) return RYOLO_EINVAL;
+bool conv_mq_plan(const ConvParams &p, int variant, ConvPlan &pl) {
+    if (!conv_mp_eligible(p)) return false;
+#ifdef RYOLO_MP_ABLATION
+    if (variant != 0 && (p.stat_part != nullptr || p.os != 1)) return false;
+#else
+    if (variant != 0) return false;
+#endif
+    const TileList t = tile_list(p, QL<64, 8>::BM, QL<64, 8>::BN);
+    if (!t.fits) return false;
+    pl.kernel = RYOLO_CONV_KERNEL_MQ;
+    pl.bm = QL<64, 8>::BM;
+    pl.variant = variant;
+    pl.grid = mq_grid_for(t.T);
+    return true;
+}
+
+int launch_conv_mq(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc) {
     const int gen = p.stat_part != nullptr ? 1 : (p.os != 1 ? 2 : 0);
 #ifdef RYOLO_MP_ABLATION
-    if (gen == 0 && variant != 0) {
-#define MQ_VAR(V) case V: return mq_launch<0, V>(p, lc);
-        switch (variant) {
+    if (pl.variant != 0) {
+#define MQ_VAR(V) case V: return mq_launch<0, V>(pl, p, lc);
+        switch (pl.variant) {
             MQ_VAR(8) MQ_VAR(16) MQ_VAR(32) MQ_VAR(40) MQ_VAR(48) MQ_VAR(1024) MQ_VAR(1056) MQ_VAR(1032) MQ_VAR(2) MQ_VAR(4) MQ_VAR(1026) MQ_VAR(1028) MQ_VAR(18) MQ_VAR(20) MQ_VAR(256) MQ_VAR(272)
             default: return RYOLO_EINVAL;
         }
 #undef MQ_VAR
     }
 #endif
-    if (variant != 0) return RYOLO_EINVAL;
     // K-tile order (kernel: advance()): channel-major (KO = 1) for the 3x3 launches whose C_in is 512 and more -- there the taps' re-reads of an
     // XCD's concurrent tiles (64 workgroups x 130 pixels x C_in x 2 B = 8.4 MB) are twice its L2 in tap-major order.  Measured on 3x3
     // 512->256 @38^2, bs 32 (profiles/r05_traffic_korder.txt): fetched bytes 420 -> 72 MB per launch (6.05 -> 1.31 x the algorithmic bytes);
@@ -786,8 +778,8 @@ int launch_conv_mq(ConvParams &p, int variant, const ConvLaunch &lc) {
     if (gen == 1) {     // statistics epilogue: the two-block order too (its row sums are flushed per block: twice as often) -- bs-64 step 50.05 vs
                         // 50.20 ms (A/B on one box, profiles/r05_ab_log.txt); RYOLO_MQ_SWEEP_STATS = 1 restores one sweep per half
         const char *es = abl_env("RYOLO_MQ_SWEEP_STATS");
-        if (es && atoi(es) == 1) return mq_launch<1, 0>(p, lc);
-        return cm ? mq_launch<1, 0, 64, 8, false, 2, 1>(p, lc) : mq_launch<1, 0, 64, 8, false, 2>(p, lc);
+        if (es && atoi(es) == 1) return mq_launch<1, 0>(pl, p, lc);
+        return cm ? mq_launch<1, 0, 64, 8, false, 2, 1>(pl, p, lc) : mq_launch<1, 0, 64, 8, false, 2>(pl, p, lc);
     }
     // The epilogue's store order (see the epilogue): two blocks of pixel groups for launches that WRITE a tensor (forward, first-writer data
     // gradients) -- HBM writes of 3x3 128->256 @76^2 at bs 32 fall from 130 to 95 MB (= the output), 1.51 -> 1.26 x the algorithmic bytes
@@ -801,11 +793,11 @@ int launch_conv_mq(ConvParams &p, int variant, const ConvLaunch &lc) {
     // (stride-2 parity classes: the same K-order rule as conv_mp.hip's launcher, so the two kernels add in the same order on every launch
     //  either of them can serve -- ADVICE r5: conv_mp took the channel-major order here and conv_mq did not)
     if (gen == 2) {
-        if (two) return cm ? mq_launch<2, 0, 64, 8, false, 2, 1>(p, lc) : mq_launch<2, 0, 64, 8, false, 2>(p, lc);
-        return cm ? mq_launch<2, 0, 64, 8, false, 1, 1>(p, lc) : mq_launch<2, 0>(p, lc);
+        if (two) return cm ? mq_launch<2, 0, 64, 8, false, 2, 1>(pl, p, lc) : mq_launch<2, 0, 64, 8, false, 2>(pl, p, lc);
+        return cm ? mq_launch<2, 0, 64, 8, false, 1, 1>(pl, p, lc) : mq_launch<2, 0>(pl, p, lc);
     }
-    if (two) return cm ? mq_launch<0, 0, 64, 8, false, 2, 1>(p, lc) : mq_launch<0, 0, 64, 8, false, 2>(p, lc);
-    return cm ? mq_launch<0, 0, 64, 8, false, 1, 1>(p, lc) : mq_launch<0, 0>(p, lc);
+    if (two) return cm ? mq_launch<0, 0, 64, 8, false, 2, 1>(pl, p, lc) : mq_launch<0, 0, 64, 8, false, 2>(pl, p, lc);
+    return cm ? mq_launch<0, 0, 64, 8, false, 1, 1>(pl, p, lc) : mq_launch<0, 0>(pl, p, lc);
 }
 
 // ---- the 128-channel members of the family (CW = 32): 128-pixel and 64-pixel tiles
@@ -814,33 +806,42 @@ bool conv_mq128_eligible(const ConvParams &p) {
            p.Kpad >= 2 * BK && p.ntaps >= 1 && p.ntaps <= 9 && p.Kpad == p.ntaps * p.Cin;
 }
 
-int conv_mq128_grid(const ConvParams &p, int bm) {
-    if ((bm != 128 && bm != 64) || (p.Cout % 128) != 0 || p.Cout / 128 > QL<32, 8>::STAT_NT) return 0;
-    return mq_grid_for(((long long)p.M + bm - 1) / bm * (p.Cout / 128), 32);
-}
-
 // The 128-channel members are instantiated in the MEASUREMENT BUILD only (round 6): built, correct, no faster than the tiles they would
 // replace (profiles/r05_mq128_bench.txt), so the shipped library neither dispatches nor contains them; tools/mq128_bench.py runs on the
 // ablation library.
-int launch_conv_mq128(ConvParams &p, int bm, const ConvLaunch &lc) {
+bool conv_mq128_plan(const ConvParams &p, int bm, bool reduce, ConvPlan &pl) {
 #ifndef RYOLO_MP_ABLATION
-    (void)p; (void)bm; (void)lc;
+    (void)p; (void)bm; (void)reduce; (void)pl;
+    return false;
+#else
+    if (!conv_mq128_eligible(p) || (bm != 128 && bm != 64)) return false;
+    // the reduce rides in the stride-1 launch without statistics; its accumulators hold STAT_NT channel tiles
+    if (reduce && (p.stat_part != nullptr || p.os != 1 || p.Cout / 128 > QL<32, 8>::STAT_NT)) return false;
+    const TileList t = tile_list(p, bm, 128);
+    if (!t.fits) return false;
+    pl.kernel = bm == 128 ? RYOLO_CONV_KERNEL_MQ128 : RYOLO_CONV_KERNEL_MQ64;
+    pl.bm = bm;
+    pl.grid = mq_grid_for(t.T, 32);
+    pl.rows = reduce ? pl.grid : 0;
+    return true;
+#endif
+}
+
+int launch_conv_mq128(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc) {
+#ifndef RYOLO_MP_ABLATION
+    (void)pl; (void)p; (void)lc;
     return RYOLO_EINVAL;
 #else
-    if (!conv_mq128_eligible(p) || (bm != 128 && bm != 64)) return RYOLO_EINVAL;
     const int gen = p.stat_part != nullptr ? 1 : (p.os != 1 ? 2 : 0);
-    if (lc.bnred) {
-        if (gen != 0) return RYOLO_EINVAL;
-        return bm == 128 ? mq_launch<0, 0, 32, 8, true>(p, lc) : mq_launch<0, 0, 32, 4, true>(p, lc);
+    if (lc.bnred) return pl.bm == 128 ? mq_launch<0, 0, 32, 8, true>(pl, p, lc) : mq_launch<0, 0, 32, 4, true>(pl, p, lc);
+    if (pl.bm == 128) {
+        if (gen == 1) return mq_launch<1, 0, 32, 8>(pl, p, lc);
+        if (gen == 2) return mq_launch<2, 0, 32, 8>(pl, p, lc);
+        return mq_launch<0, 0, 32, 8>(pl, p, lc);
     }
-    if (bm == 128) {
-        if (gen == 1) return mq_launch<1, 0, 32, 8>(p, lc);
-        if (gen == 2) return mq_launch<2, 0, 32, 8>(p, lc);
-        return mq_launch<0, 0, 32, 8>(p, lc);
-    }
-    if (gen == 1) return mq_launch<1, 0, 32, 4>(p, lc);
-    if (gen == 2) return mq_launch<2, 0, 32, 4>(p, lc);
-    return mq_launch<0, 0, 32, 4>(p, lc);
+    if (gen == 1) return mq_launch<1, 0, 32, 4>(pl, p, lc);
+    if (gen == 2) return mq_launch<2, 0, 32, 4>(pl, p, lc);
+    return mq_launch<0, 0, 32, 4>(pl, p, lc);
 #endif
 }
 

@@ -597,8 +597,6 @@ int pw_launch_mode(ConvParams &p, const PwBnRed *br, int grid, hipStream_t strea
     return RYOLO_EINVAL;
 }
 
-inline unsigned pw_magic_u32(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
-
 // which configuration serves (K, C_out, M); returns false when none does.  NB = channel blocks, wgpc = workgroups per CU.
 bool pw_pick(const ConvParams &p, bool bnred, PwCfg &c, int &NB, int &grid) {
     if (p.Kpad != p.Cin || (p.Cin & 63)) return false;
@@ -644,7 +642,33 @@ bool pw_pick(const ConvParams &p, bool bnred, PwCfg &c, int &NB, int &grid) {
 
 namespace ryolo_detail {
 
-bool conv_pw_eligible(const ConvParams &p, int ksize) {
+// what a launch of `p` is: its configuration, channel blocks, grid, row blocks and tensor extents.  fits: a configuration serves the
+// shape and every tensor slice (the look-ahead of one workgroup stride past the last row block included) is within 31-bit byte offsets.
+// The plan (conv_pw_plan, the decoded head) asks that; pw_run() takes the fields.
+struct PwLaunch {
+    PwCfg c;
+    int NB, grid;
+    long long mb;
+    unsigned y_bytes, res_bytes;
+    bool fits;
+};
+static PwLaunch pw_launch_shape(const ConvParams &p, bool bnred) {
+    PwLaunch l{};
+    if (!pw_pick(p, bnred, l.c, l.NB, l.grid)) return l;
+    const int bms = l.c.pf * 16;
+    l.mb = ((long long)p.M + bms - 1) / bms;
+    const unsigned long long yb = (((unsigned long long)p.M * p.ups * p.ups - 1) * p.out_cs + p.Cout) * 2ull;
+    const unsigned long long rb = p.res ? (((unsigned long long)p.M - 1) * p.res_cs + p.Cout) * 2ull : 0ull;
+    const unsigned long long xmax = ((unsigned long long)(l.mb + l.grid) * bms) * p.in_cs * 2ull + 4096;
+    l.fits = yb < 0x7fffff00ull && rb < 0x7fffff00ull && xmax < 0x7fffff00ull && l.mb <= 0x7fffffffll &&
+             (p.ups == 1 || (long long)l.mb * bms * (p.Wo > p.Ho ? p.Wo : p.Ho) < 0x100000000ll) && !(bnred && (p.stat_part || p.ups != 1));
+    l.y_bytes = (unsigned)yb;
+    l.res_bytes = (unsigned)rb;
+    return l;
+}
+static int pw_run(const PwLaunch &l, ConvParams &p, const ConvLaunch &lc);
+
+static bool conv_pw_eligible(const ConvParams &p, int ksize) {
     if (ksize != 1 || !p.fast || p.os != 1 || p.stride != 1 || p.taps2) return false;
     if (p.stat_part && (p.res || p.ups != 1)) return false;
     if (p.res && p.ups != 1) return false;
@@ -667,11 +691,14 @@ bool conv_pw_preferred(const ConvParams &p) {
     return c.kt <= 12 && 2 * p.Cout <= 3 * p.Cin && mb * NB >= 2ll * grid;
 }
 
-// rows of BatchNorm-reduce partials (= workgroups) a conv_pw launch of this shape writes; 0 = not served
-int conv_pw_grid(const ConvParams &p) {
-    PwCfg c;
-    int NB, grid;
-    return pw_pick(p, true, c, NB, grid) ? grid : 0;
+bool conv_pw_plan(const ConvParams &p, int ksize, bool reduce, ConvPlan &pl) {
+    if (!conv_pw_eligible(p, ksize)) return false;
+    const PwLaunch l = pw_launch_shape(p, reduce);
+    if (!l.fits) return false;
+    pl.kernel = RYOLO_CONV_KERNEL_PW;
+    pl.grid = l.grid;
+    pl.rows = reduce ? l.grid : 0;
+    return true;
 }
 
 // anchors per channel block of a decoded head: the most whole anchors that fit in the block's `ncb` channels
@@ -702,7 +729,8 @@ int launch_conv_pw_decode(ConvParams &p, float *io, long long io_img_rows, long 
     g_pw_decode = &dc;
     ConvLaunch lc;
     lc.stream = stream;
-    const int rc = launch_conv_pw(p, lc);
+    const PwLaunch l = pw_launch_shape(p, false);
+    const int rc = l.fits ? pw_run(l, p, lc) : RYOLO_EINVAL;
     g_pw_decode = nullptr;
     return rc;
 }
@@ -733,40 +761,32 @@ static int g_pw_dbg = 0;
 static unsigned *g_pw_trace = nullptr;
 #endif
 
-int launch_conv_pw(ConvParams &p, const ConvLaunch &lc) {
+int launch_conv_pw(const ConvPlan &, ConvParams &p, const ConvLaunch &lc) { return pw_run(pw_launch_shape(p, lc.bnred != nullptr), p, lc); }
+
+static int pw_run(const PwLaunch &l, ConvParams &p, const ConvLaunch &lc) {
 #ifdef RYOLO_MP_ABLATION
     p.dbg0 = g_pw_dbg;
     p.trace = g_pw_trace;
 #endif
-    PwCfg c;
-    int NB, grid;
-    if (!pw_pick(p, lc.bnred != nullptr, c, NB, grid)) return RYOLO_EINVAL;
-    const int bms = c.pf * 16;
-    const long long mb = ((long long)p.M + bms - 1) / bms;
-    const unsigned long long yb = (((unsigned long long)p.M * p.ups * p.ups - 1) * p.out_cs + p.Cout) * 2ull;
-    const unsigned long long rb = p.res ? (((unsigned long long)p.M - 1) * p.res_cs + p.Cout) * 2ull : 0ull;
-    // 32-bit byte offsets everywhere, including the look-ahead of one workgroup stride past the last row block
-    const unsigned long long xmax = ((unsigned long long)(mb + grid) * bms) * p.in_cs * 2ull + 4096;
-    if (yb >= 0x7fffff00ull || rb >= 0x7fffff00ull || xmax >= 0x7fffff00ull || mb > 0x7fffffffll) return RYOLO_EINVAL;
-    if (p.ups != 1 && (long long)mb * bms * (p.Wo > p.Ho ? p.Wo : p.Ho) >= 0x100000000ll) return RYOLO_EINVAL;
-    p.y_bytes = (unsigned)yb;
-    p.res_bytes = (unsigned)rb;
-    p.pw_nb = NB;
-    p.pw_mb = (int)mb;
-    p.magic_wo = pw_magic_u32(p.Wo);
-    p.magic_ho = pw_magic_u32(p.Ho);
+    const PwCfg c = l.c;
+    const int grid = l.grid;
+    p.y_bytes = l.y_bytes;
+    p.res_bytes = l.res_bytes;
+    p.pw_nb = l.NB;
+    p.pw_mb = (int)l.mb;
+    p.magic_wo = magic_u32(p.Wo);
+    p.magic_ho = magic_u32(p.Ho);
     PwBnRed br{};
     const PwBnRed *brp = nullptr;
     if (const BnRed *b = lc.bnred) {
-        if (p.stat_part || p.ups != 1) return RYOLO_EINVAL;
         br.z = b->z; br.z_cs = b->z_cs; br.scale = b->scale; br.shift = b->shift; br.mean = b->mean; br.invstd = b->invstd;
         br.slope = b->slope; br.part = b->part;
-        const unsigned long long zb = (((unsigned long long)p.M - 1) * b->z_cs + p.Cout) * 2ull;
-        if (zb >= 0x7fffff00ull) return RYOLO_EINVAL;
-        br.z_bytes = (unsigned)zb;
+        // z is read through a buffer descriptor; its stride is an argument of the launch, not of the plan: beyond 31-bit offsets is the
+        // caller's invalid argument
+        if (!buffer_extent(p.M, b->z_cs, p.Cout, &br.z_bytes)) return RYOLO_EINVAL;
         brp = &br;
     }
-    RYOLO_CONV_DRY_RUN(lc, RYOLO_CONV_KERNEL_PW);       // (a mode without an instantiation returns EINVAL below: the forward modes all exist)
+    // (a mode without an instantiation returns EINVAL below: the forward modes and the reduce's configurations all exist)
 #define PW_CASE(KT_, NW_, CF_, PF_, RING_, MODES_)                                               \
     if (c.kt == KT_ && c.nw == NW_ && c.cf == CF_ && c.pf == PF_ && c.ring == RING_)              \
         return pw_launch_mode<KT_, NW_, CF_, PF_, RING_, MODES_>(p, brp, grid, lc.stream);

@@ -943,29 +943,43 @@ int launch_stem(ConvParams &p, int grid, int tiles_x, int tiles_y, int ntiles, h
 
 }  // namespace
 
-bool conv_stem_eligible(const ConvParams &p, int ksize) {
-    return ksize == 3 && p.Cin == CIN && p.Cout == COUT && p.pad == 1 && (p.stride == 1 || p.stride == 2) && p.fast && p.os == 1 &&
-           p.ups == 1 && p.ntaps == 9 && (p.in_cs & 7) == 0 && (p.out_cs & 7) == 0 && (!p.res || (p.res_cs & 7) == 0) &&
-           !(p.stat_part && p.res) && (long long)p.N * p.H * p.W * p.in_cs * 2 < 0x7fffff00ll;
+// the persistent grid of the stem kernels: two workgroups per CU, a multiple of 8 (XCD chunking)
+static int stem_grid() {
+    const int grid = (2 * cu_count()) & ~7;
+    return grid < 8 ? 8 : grid;
+}
+// the tile list of `p` in th x tw output tiles
+static long long stem_tiles(const ConvParams &p, int th, int tw, int &tiles_x, int &tiles_y) {
+    tiles_x = (p.Wo + tw - 1) / tw;
+    tiles_y = (p.Ho + th - 1) / th;
+    return (long long)p.N * tiles_x * tiles_y;
+}
+static int stem_th(const ConvParams &p) { return p.stride == 1 ? Patch<1>::TH : Patch<2>::TH; }
+
+// a 3x3 pad-1 cin -> cout layer as the halo kernels take it (max_stride: 2 where the kernel has a stride-2 form) in th x tw tiles
+static bool stem_plan(const ConvParams &p, int ksize, int cin, int cout, int max_stride, int th, int tw, int kernel, ConvPlan &pl) {
+    int tx, ty;
+    if (!(ksize == 3 && p.Cin == cin && p.Cout == cout && p.pad == 1 && p.stride >= 1 && p.stride <= max_stride && p.fast && p.os == 1 &&
+          p.ups == 1 && p.ntaps == 9 && (p.in_cs & 7) == 0 && (p.out_cs & 7) == 0 && (!p.res || (p.res_cs & 7) == 0) &&
+          !(p.stat_part && p.res) && (long long)p.N * p.H * p.W * p.in_cs * 2 < 0x7fffff00ll) ||
+        stem_tiles(p, th, tw, tx, ty) > 0x7fffffffll)
+        return false;
+    pl.kernel = kernel;
+    pl.grid = stem_grid();
+    return true;
+}
+bool conv_stem_plan(const ConvParams &p, int ksize, ConvPlan &pl) { return stem_plan(p, ksize, CIN, COUT, 2, stem_th(p), TW, RYOLO_CONV_KERNEL_STEM, pl); }
+bool conv_stem64_plan(const ConvParams &p, int ksize, ConvPlan &pl) {
+    return stem_plan(p, ksize, c64::CIN, c64::COUT, 1, c64::TH, c64::TWX, RYOLO_CONV_KERNEL_STEM64, pl);
 }
 
-bool conv_stem64_eligible(const ConvParams &p, int ksize) {
-    return ksize == 3 && p.Cin == c64::CIN && p.Cout == c64::COUT && p.pad == 1 && p.stride == 1 && p.fast && p.os == 1 &&
-           p.ups == 1 && p.ntaps == 9 && (p.in_cs & 7) == 0 && (p.out_cs & 7) == 0 && (!p.res || (p.res_cs & 7) == 0) &&
-           !(p.stat_part && p.res) && (long long)p.N * p.H * p.W * p.in_cs * 2 < 0x7fffff00ll;
-}
-
-int launch_conv_stem64(ConvParams &p, const ConvLaunch &lc) {
-    const int tiles_x = (p.Wo + c64::TWX - 1) / c64::TWX, tiles_y = (p.Ho + c64::TH - 1) / c64::TH;
-    const long long nt = (long long)p.N * tiles_x * tiles_y;
-    if (nt > 0x7fffffffll) return RYOLO_EINVAL;
-    RYOLO_CONV_DRY_RUN(lc, RYOLO_CONV_KERNEL_STEM64);
-    int grid = (2 * cu_count()) & ~7;
-    if (grid < 8) grid = 8;
-    if (p.stat_part) return launch_stem64<true, RYOLO_ACT_LINEAR>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream);
-    if (p.act == RYOLO_ACT_LEAKY) return launch_stem64<false, RYOLO_ACT_LEAKY>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream);
-    if (p.act == RYOLO_ACT_MISH) return launch_stem64<false, RYOLO_ACT_MISH>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream);
-    return launch_stem64<false, RYOLO_ACT_LINEAR>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream);
+int launch_conv_stem64(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc) {
+    int tiles_x, tiles_y;
+    const int nt = (int)stem_tiles(p, c64::TH, c64::TWX, tiles_x, tiles_y), grid = pl.grid;
+    if (p.stat_part) return launch_stem64<true, RYOLO_ACT_LINEAR>(p, grid, tiles_x, tiles_y, nt, lc.stream);
+    if (p.act == RYOLO_ACT_LEAKY) return launch_stem64<false, RYOLO_ACT_LEAKY>(p, grid, tiles_x, tiles_y, nt, lc.stream);
+    if (p.act == RYOLO_ACT_MISH) return launch_stem64<false, RYOLO_ACT_MISH>(p, grid, tiles_x, tiles_y, nt, lc.stream);
+    return launch_stem64<false, RYOLO_ACT_LINEAR>(p, grid, tiles_x, tiles_y, nt, lc.stream);
 }
 
 // The stride-2 data gradient one level down (Darknet-53 layer 5: 3x3 / 2, 64 -> 128; 128 -> 64 channels in the gradient's direction).  The filter (9 x 128 x 64 bf16 = 147 KB) only fits the registers of a workgroup if the WAVES SPLIT THE OUTPUT
@@ -1087,28 +1101,46 @@ __global__ void __launch_bounds__(256, 2) dgrad3x3_s2_c128_kernel(const DgS2Para
     }
 }
 
-int launch_conv_stem_dgrad(int cdz, int stride, const void *dz, int dz_cs, const void *w_classes, void *dx, int dx_cs, int accumulate, int N,
-                           int H, int W, int nt_out, const ConvLaunch &lc) {
+// the launch of the stem data gradient of `d` (the FORWARD conv: 3x3 pad 1, 32 -> 64 stride 1 / 2 or 64 -> 128 stride 2) over a dz of pixel
+// stride dz_cs: geometry, tile list and extents; false: another shape, or dz / dx / the tile list beyond 31-bit offsets
+static bool stem_dgrad_params(const ryolo_conv_desc *d, int dz_cs, DgS2Params &q) {
+    const int cdz = d->Cout, stride = d->stride, N = d->N, H = d->H, W = d->W;
+    if (d->ksize != 3 || d->pad != 1 || !((d->Cin == 32 && cdz == 64 && (stride == 1 || stride == 2)) || (d->Cin == 64 && cdz == 128 && stride == 2)))
+        return false;
     const int Ho = stride == 2 ? (H - 1) / 2 + 1 : H, Wo = stride == 2 ? (W - 1) / 2 + 1 : W;
-    const unsigned long long dzb = (((unsigned long long)N * Ho * Wo - 1) * dz_cs + cdz) * 2ull;
-    if ((stride != 1 && stride != 2) || (cdz != 64 && !(cdz == 128 && stride == 2)) || dzb >= 0x7fffff00ull || (dz_cs & 7) || (dx_cs & 7) || dz_cs < cdz ||
-        dx_cs < cdz / 2)
-        return RYOLO_EINVAL;
-    DgS2Params q;
-    q.dz = (const __bf16 *)dz; q.dz_bytes = (unsigned)dzb; q.dz_cs = dz_cs; q.w = (const __bf16 *)w_classes;
-    q.dx = (__bf16 *)dx; q.dx_cs = dx_cs; q.res = accumulate ? (const __bf16 *)dx : nullptr;
+    if ((dz_cs & 7) || (d->in_cstride & 7) || dz_cs < cdz || d->in_cstride < cdz / 2) return false;
+    if (!buffer_extent((unsigned long long)N * Ho * Wo, dz_cs, cdz, &q.dz_bytes) || !buffer_extent((unsigned long long)N * H * W, d->in_cstride, d->Cin))
+        return false;
+    q.dz_cs = dz_cs; q.dx_cs = d->in_cstride;
     q.H = H; q.W = W; q.Ho = Ho; q.Wo = Wo;
     const int th = cdz == 64 ? (stride == 2 ? DgTile<2>::TH : DgTile<1>::TH) : DgTile128::TH;
     const int tw = cdz == 64 ? (stride == 2 ? DgTile<2>::TW : DgTile<1>::TW) : DgTile128::TW;
     q.tiles_x = (W + tw - 1) / tw; q.tiles_y = (H + th - 1) / th;
     const long long nt = (long long)q.tiles_x * q.tiles_y * N;
-    if (nt >= 0x7fffffff) return RYOLO_EINVAL;
-    q.ntiles = (int)nt; q.nt_out = nt_out;
-    int grid = (2 * cu_count()) & ~7;
-    if (grid < 8) grid = 8;
-    const dim3 g((unsigned)grid), b(256);
-    if (cdz == 128) return launch_kernel<dgrad3x3_s2_c128_kernel>(g, b, 2 * DgTile128::BUF, lc.stream, q);
-    if (stride == 2) return launch_kernel<dgrad3x3_c64_kernel<2>>(g, b, 2 * DgTile<2>::BUF, lc.stream, q);
+    if (nt >= 0x7fffffff) return false;
+    q.ntiles = (int)nt;
+    return true;
+}
+
+bool conv_stem_dgrad_plan(const ryolo_conv_desc *d, int dz_cs, ConvPlan &pl) {
+    DgS2Params q;
+    if (!stem_dgrad_params(d, dz_cs, q)) return false;
+    pl.kernel = RYOLO_CONV_KERNEL_STEM_DGRAD;
+    pl.ksize = 3;
+    pl.grid = stem_grid();
+    return true;
+}
+
+int launch_conv_stem_dgrad(const ConvPlan &pl, const ryolo_conv_desc *d, const void *dz, int dz_cs, const void *w_classes, void *dx, int accumulate,
+                           int nt_out, const ConvLaunch &lc) {
+    DgS2Params q;
+    stem_dgrad_params(d, dz_cs, q);      // (the shared derivation conv_stem_dgrad_plan accepted)
+    q.dz = (const __bf16 *)dz; q.w = (const __bf16 *)w_classes;
+    q.dx = (__bf16 *)dx; q.res = accumulate ? (const __bf16 *)dx : nullptr;
+    q.nt_out = nt_out;
+    const dim3 g((unsigned)pl.grid), b(256);
+    if (d->Cout == 128) return launch_kernel<dgrad3x3_s2_c128_kernel>(g, b, 2 * DgTile128::BUF, lc.stream, q);
+    if (d->stride == 2) return launch_kernel<dgrad3x3_c64_kernel<2>>(g, b, 2 * DgTile<2>::BUF, lc.stream, q);
     return launch_kernel<dgrad3x3_c64_kernel<1>>(g, b, 2 * DgTile<1>::BUF, lc.stream, q);
 }
 
@@ -1124,18 +1156,13 @@ int launch_conv0_halo(ConvParams &p, const float *slope_dev, int round_z, const 
     return launch_conv0_halo_t(p, slope_dev, round_z, p.act, grid, tiles_x, tiles_y, (int)nt, lc.stream);
 }
 
-int launch_conv_stem(ConvParams &p, const ConvLaunch &lc) {
-    const int th = p.stride == 1 ? Patch<1>::TH : Patch<2>::TH;
-    const int tiles_x = (p.Wo + TW - 1) / TW, tiles_y = (p.Ho + th - 1) / th;
-    const long long nt = (long long)p.N * tiles_x * tiles_y;
-    if (nt > 0x7fffffffll) return RYOLO_EINVAL;
-    RYOLO_CONV_DRY_RUN(lc, RYOLO_CONV_KERNEL_STEM);
-    int grid = (2 * cu_count()) & ~7;
-    if (grid < 8) grid = 8;
-    if (p.stat_part) return p.stride == 1 ? launch_stem<1, true>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream)
-                                          : launch_stem<2, true>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream);
-    return p.stride == 1 ? launch_stem<1, false>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream)
-                         : launch_stem<2, false>(p, grid, tiles_x, tiles_y, (int)nt, lc.stream);
+int launch_conv_stem(const ConvPlan &pl, ConvParams &p, const ConvLaunch &lc) {
+    int tiles_x, tiles_y;
+    const int nt = (int)stem_tiles(p, stem_th(p), TW, tiles_x, tiles_y), grid = pl.grid;
+    if (p.stat_part) return p.stride == 1 ? launch_stem<1, true>(p, grid, tiles_x, tiles_y, nt, lc.stream)
+                                          : launch_stem<2, true>(p, grid, tiles_x, tiles_y, nt, lc.stream);
+    return p.stride == 1 ? launch_stem<1, false>(p, grid, tiles_x, tiles_y, nt, lc.stream)
+                         : launch_stem<2, false>(p, grid, tiles_x, tiles_y, nt, lc.stream);
 }
 
 static int launch_pair(ConvParams &p, const PairFirst &f, hipStream_t stream) {

@@ -148,7 +148,7 @@ class HipEngine(object):
                 t = op['desc']
                 cv, res, ups = conv_params(i, t[3], op.get('src')), tv(op['res']), op['ups']
                 self.ops.append(self._mk_conv(xin, cv['packed'], cv['scale'], cv['shift'], t[4], t[5], t[6], t[7], t[11], t[12], res, out, ups))
-                # the kernel the library's dispatch takes for this launch (dry run of csrc/conv.hip dispatch())
+                # the kernel the library's dispatch takes for this launch (csrc/conv_dispatch.hip conv_plan(): the plan the launch executes)
                 info.update(name=ops.conv_kernel_name(*t[:8], in_cs=t[8], out_cs=t[9], res_cs=t[10], upsample=ups, residual=res is not None),
                             flops=flops(cv, shp[i]),
                             bytes=2.0 * self.bs * (t[1] * t[2] * cv['cin'] + shp[i][1] * shp[i][2] * t[4] * (ups * ups + (1 if res is not None else 0)))

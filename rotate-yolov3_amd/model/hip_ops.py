@@ -188,7 +188,7 @@ _IGEMM_TILES = {1: '128x128', 2: '256x64', 3: '256x32', 4: '256x128', 6: '128x12
 
 def conv_kernel_name(n, h, w, cin, cout, ksize, stride=1, pad=None, in_cs=None, out_cs=None, res_cs=0, upsample=1, tile=0,
                      residual=False, statistics=False):
-    """Name of the kernel the library's dispatch picks for this conv on the current device (a dry run, nothing is launched):
+    """Name of the kernel the library's dispatch picks for this conv on the current device (the launch's plan, nothing is launched):
     what the per-kernel tables of bench.py and the profiles call it."""
     pad = (ksize - 1) // 2 if pad is None else pad
     d = ConvDesc(n, h, w, cin, cout, ksize, stride, pad, in_cs or cin, out_cs or cout, res_cs or (cout if residual else 0), 1, 0.1,

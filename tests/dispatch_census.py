@@ -162,12 +162,12 @@ def _gemm_bits(code, M, Cout, ks, cus, stats, res, os_, force, kpad):
         bm = 128 if code == 9 else 64
         T = -(-M // bm) * -(-Cout // 128)
         return (M % bm != 0, Cout % 128 != 0) + _grid_bits(T, 2 * (cus & ~7))
-    if code >= 16:              # conv.hip igemm_tile_code(); launch_variant()'s persistent grid (conv_common.h persist_grid())
+    if code >= 16:              # conv_common.h IGEMM_TILES; conv.hip conv_igemm_plan()'s persistent grid (conv_common.h persist_grid())
         bm, bn, waves, nst = {1: (128, 128, 8, 2), 2: (256, 64, 4, 2), 3: (256, 32, 4, 2), 4: (256, 128, 8, 3), 6: (128, 128, 8, 2),
                               7: (128, 128, 4, 2)}[code - 16]
         T = -(-M // bm) * -(-Cout // bn)
         grid = (2 * cus) & ~7
-        # conv.hip dispatch(): the 1x1 128 x 128 auto pick leaves the persistent layout to the 4-wave tile; its short-K 3x3 rule sets force_persist
+        # conv_dispatch.hip conv_plan(): the 1x1 128 x 128 pick leaves the persistent layout to the 4-wave tile; its short-K 3x3 rule forces the persistent grid
         no_persist = code == 17 and ks == 1
         persist_ok = os_ == 1 and (not stats or (waves == 4 and not res))
         persistent = False
@@ -274,6 +274,148 @@ def wgrad_plan_hashes(groups=None):
     return {k: hashlib.sha256(json.dumps(rows).encode()).hexdigest() for k, rows in groups.items()}
 
 
+# ------------------------------------------------------------------------------------------------ the convolutions' host decisions
+CONV_PLAN_PICKS = tuple(range(1, 18)) + (13 | (2 << 16),)            # every forced tile low byte; conv_pw.hip with a capped grid
+CONV_PLAN_BITS = (0x100, 0x200, 0x800, 0x8000)                        # general path; no persistent grid; forced persistent grid; classic dgrad classes
+CONV_PLAN_TUNES = (("RYOLO_CONV3X3", ("mp", "mq")), ("RYOLO_CONV1X1", ("igemm",)), ("RYOLO_BN_REDUCE_TILES", ("0", "2")),
+                   ("RYOLO_STEM_DGRAD", ("0", "1", "2")))
+CONV_PLAN_BASE = ((608, 608, 64, True), (608, 608, 1, True), (320, 320, 1, True), (608, 608, 32, False))     # (H, W, N, with the training plan)
+PIXELS_MAX = 0x7fffffff - 512          # conv_dispatch.hip conv_shape(): the most pixels one launch indexes
+SLICE_MAX = 1 << 31                    # bytes a tensor slice must stay below for the kernels' 31-bit buffer offsets
+
+
+def _full(t):
+    return desc_tuple(mk_desc(t))
+
+
+def _with(t, **kw):
+    return tuple(kw.get(f, v) for f, v in zip(DESC_FIELDS, t))
+
+
+def dgrad_pixels(t):
+    """pixels of the input gradient a data gradient of descriptor `t` writes"""
+    return t[0] * t[1] * t[2]
+
+
+def conv_plan_record(t):
+    """every host decision the library's queries show for one conv descriptor: the forward kernel for (residual, statistics) in (0,0),
+    (1,0), (0,1), (1,1); the data gradient's kernel plain and with the folded BatchNorm reduce, and the reduce's rows (None where the
+    input gradient has more pixels than a launch indexes: those are refused, test_dispatch_census.py asserts that apart); whether the
+    layer-0 recompute serves it"""
+    L, d = _L(), mk_desc(t)
+    fwd = [L.ryolo_conv_kernel_choice(C.byref(d), r, s) for s in (0, 1) for r in (0, 1)]
+    if dgrad_pixels(t) > PIXELS_MAX:
+        dg = [None, None, None]
+    else:
+        dg = [L.ryolo_conv_dgrad_kernel_choice(C.byref(d), 0), L.ryolo_conv_dgrad_kernel_choice(C.byref(d), 1), L.ryolo_conv2d_dgrad_bnreduce_rows(C.byref(d))]
+    return fwd + dg + [L.ryolo_conv0_recompute_supported(C.byref(d))]
+
+
+def _plan_points(defs, H, W, N, train):
+    """(descriptors, fused ops) of the engines' plans at one point: the ops are ("pair", first, second, shortcut) / ("head", desc, na, no)"""
+    descs, fused = set(), set()
+    recs = eval_blocks(defs, H, W, N) + (train_blocks(defs, H, W, N) if train else [])
+    for r in recs:
+        if r["form"] == "pair":
+            a, b = (_full(x) for x in r["descs"])
+            descs.update((a, b))
+            fused.add(("pair", a, b, 1 if r["shortcut"] else 0))
+        elif r["form"] == "head":
+            descs.add(_full(r["desc"]))
+            fused.add(("head", _full(r["desc"]), r["na"], r["no"]))
+        else:
+            descs.add(_full(r["desc"]))
+    return descs, fused
+
+
+def _conv_plan_rows(descs, fused=()):
+    L = _L()
+    rows = [list(t) + conv_plan_record(t) for t in sorted(descs)]
+    for op in sorted(fused):
+        if op[0] == "pair":
+            rows.append(["pair"] + list(op[1]) + list(op[2]) + [op[3], L.ryolo_conv_pair_supported(C.byref(mk_desc(op[1])), C.byref(mk_desc(op[2])), op[3])])
+        else:
+            rows.append(["head"] + list(op[1]) + [op[2], op[3], L.ryolo_conv_head_decode_supported(C.byref(mk_desc(op[1])), op[2], op[3])])
+    return rows
+
+
+def _raised_cstride(pixels, channels):
+    """the smallest multiple of 8 at which `pixels` pixels of that stride, the last one `channels` wide, reach SLICE_MAX bytes"""
+    cs = -(-(SLICE_MAX // 2 - channels) // (pixels - 1))
+    return max(-(-cs // 8) * 8, -(-channels // 8) * 8)
+
+
+def conv_guard_variants(t):
+    """{name: descriptor}: `t` pushed over each size guard of the dispatch in turn"""
+    N, H, W, Cin, Cout = t[:5]
+    Ho, Wo = _out_hw(t)
+    ups = t[DESC_FIELDS.index("upsample")]
+    out = {"out_cstride": _with(t, out_cstride=_raised_cstride(N * Ho * Wo * ups * ups, Cout)),
+           "in_cstride": _with(t, in_cstride=_raised_cstride(N * H * W, Cin)),
+           "res_cstride": _with(t, res_cstride=_raised_cstride(N * Ho * Wo, Cout))}
+    n = -(-(1 << 32) // (Ho * Wo * max(Ho, Wo)))               # M * max(Ho, Wo) >= 2^32: the multiply-high pixel split is no longer exact
+    if n * Ho * Wo <= PIXELS_MAX:
+        out["pixel_extent"] = _with(t, N=n)
+    out["pixels"] = _with(t, N=PIXELS_MAX // (Ho * Wo) + 1)     # M > PIXELS_MAX
+    return out
+
+
+def conv_plan_groups(configs=CONFIGS, sizes=SIZES, batches=BATCHES):
+    """{group: rows}: the host decisions of the forward convolution and the data gradient (conv_plan_record per descriptor; the fused
+    pair / head ops of the plans with their *_supported answers)
+      auto/config/classes/HxW   every distinct descriptor of eval_blocks and train_blocks over `batches`
+      pick/v, bit/0x..          the base set (CONV_PLAN_BASE, darknet53 with one class) under each forced tile low byte / tile bit
+      tune/NAME=value           the base set under each tuning switch (set through ryolo_set_tuning, cleared after the group)
+      guard/name                the 608^2 bs-64 descriptors pushed over each size guard (conv_guard_variants)"""
+    groups = {}
+    for kind, nc in configs:
+        for (H, W) in sizes:
+            defs = config_defs(kind, nc, H, W)
+            descs, fused = set(), set()
+            for N in batches:
+                try:
+                    d, f = _plan_points(defs, H, W, N, kind == "darknet53")
+                except Refused:
+                    continue
+                descs |= d
+                fused |= f
+            groups["auto/%s/%d/%dx%d" % (kind, nc, H, W)] = _conv_plan_rows(descs, fused)
+    base, base_fused, bs64 = set(), set(), set()
+    for (H, W, N, train) in CONV_PLAN_BASE:
+        d, f = _plan_points(config_defs("darknet53", 1, H, W), H, W, N, train)
+        base |= d
+        base_fused |= f
+        if N == 64:
+            bs64 |= d
+    ti = DESC_FIELDS.index("tile")
+    for v in CONV_PLAN_PICKS:
+        groups["pick/%d" % v] = _conv_plan_rows(set(_with(t, tile=v) for t in base))
+    for b in CONV_PLAN_BITS:
+        groups["bit/0x%x" % b] = _conv_plan_rows(set(_with(t, tile=t[ti] | b) for t in base))
+    for name, values in CONV_PLAN_TUNES:
+        for v in values:
+            _lib.set_tuning(name, v)
+            try:
+                groups["tune/%s=%s" % (name, v)] = _conv_plan_rows(base, base_fused)
+            finally:
+                _lib.set_tuning(name, None)
+    guards = {}
+    for t in sorted(bs64):
+        for name, g in conv_guard_variants(t).items():
+            guards.setdefault(name, set()).add(g)
+    for name, descs in guards.items():
+        groups["guard/%s" % name] = _conv_plan_rows(descs)
+    return groups
+
+
+def conv_plan_hashes(groups=None):
+    """one sha256 per group of conv_plan_groups(): tests/golden/conv_plan.json holds the parent library's"""
+    import hashlib
+    import json
+    groups = conv_plan_groups() if groups is None else groups
+    return {k: hashlib.sha256(json.dumps(rows).encode()).hexdigest() for k, rows in groups.items()}
+
+
 def edge_bits(rec, cus):
     """named boolean edge bits of one census record"""
     form, code, t = rec["form"], rec["code"], rec.get("desc")
@@ -321,7 +463,7 @@ def edge_bits(rec, cus):
         if code == 6:
             return dict(zip(names4, _pw_bits(M, Cout, Cin, cus)))
         kpad = -(-(k * k * Cin) // BK) * BK
-        force = k == 3 and kpad // BK <= 9 and not (stats and (res or code == 18))    # conv.hip dispatch(): the short-K 3x3 rule
+        force = k == 3 and kpad // BK <= 9 and not (stats and (res or code == 18))    # conv_dispatch.hip conv_plan(): the short-K 3x3 rule
         bits = _gemm_bits(code, M, Cout, k, cus, stats, res, 1, force, kpad)
         return dict(zip(names4, bits), part_cstride=out_cs != Cout, idle_wgs=_idle_wgs(code, M, Cout, cus))
     if form == "dgrad":

@@ -129,6 +129,41 @@ def test_wgrad_host_decisions_match_the_golden():
     assert not differ, "weight-gradient host decisions changed in %s" % differ
 
 
+def test_conv_host_decisions_match_the_golden():
+    """The kernel every forward convolution and data gradient takes (with and without residual, statistics and the folded BatchNorm
+    reduce), the reduce's rows and the fused-op answers -- over the census's input space and, for a base set of plans, under every forced
+    tile, tile bit, tuning switch and size guard -- are the ones the library gave before its dispatch was rewritten around one plan:
+    tests/golden/conv_plan.json holds one hash per group, generated from the parent commit's library by
+    tests/golden/gen_conv_plan_golden.py."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_plan.json")) as fh:
+        want = json.load(fh)["groups"]
+    got = dc.conv_plan_hashes()
+    assert sorted(got) == sorted(want)
+    n_tune = sum(len(v) for _, v in dc.CONV_PLAN_TUNES)
+    assert len(want) == len(dc.CONFIGS) * len(dc.SIZES) + len(dc.CONV_PLAN_PICKS) + len(dc.CONV_PLAN_BITS) + n_tune + 5
+    differ = [k for k in sorted(want) if got[k] != want[k]]
+    assert not differ, "convolution host decisions changed in %s" % differ
+
+
+def test_data_gradient_refuses_more_pixels_than_a_launch_indexes():
+    """The rows the golden records without data-gradient fields: an input gradient of more than 2^31 - 512 pixels.  The forward refuses
+    such an output (conv_shape); the data gradient builds its launches through the same shape code and refuses too -- no kernel, no rows."""
+    L = dc._L()
+    groups = dc.conv_plan_groups(configs=(), sizes=(), batches=())
+    rows = [r for g in groups.values() for r in g if r[0] not in ("pair", "head")]
+    n = len(dc.DESC_FIELDS)
+    big = [tuple(r[:n]) for r in rows if dc.dgrad_pixels(r) > dc.PIXELS_MAX]
+    # every descriptor of guard/pixels is one (its forward output alone has too many pixels), stride-2 and 1x1 layers among them
+    assert groups["guard/pixels"] and all(tuple(r[:n]) in big for r in groups["guard/pixels"])
+    assert any(t[6] == 2 for t in big) and any(t[5] == 1 for t in big)
+    for t in big:
+        d = dc.mk_desc(t)
+        got = (L.ryolo_conv_dgrad_kernel_choice(C.byref(d), 0), L.ryolo_conv_dgrad_kernel_choice(C.byref(d), 1), L.ryolo_conv2d_dgrad_bnreduce_rows(C.byref(d)))
+        assert got == (-1, -1, 0), (t, got)
+
+
 def test_wgrad_queries_answer_the_same_from_two_threads():
     """The weight gradient's queries compute one plan per call and keep nothing between calls: two threads asking the kernel choice, the
     workspace size and the reduce job of the bs-64 training blocks at once, in opposite order, get the serial answers."""

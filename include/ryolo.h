@@ -253,12 +253,15 @@ int ryolo_yolo_decode_filter(const void *head, int head_cstride, int bs, int ny,
  * (model/model_utils.py:16-35).  `head`: NHWC bf16 output of the last 1x1 conv, channel = a*no + k, no = nc+6.
  *   io [bs, io_rows_per_image, no] fp32: rows io_row_offset + (a*ny + y)*nx + x receive the decoded
  *        (x, y, w, h, angle, obj, cls...) in pixels (the three heads write into one tensor: the torch.cat of
- *        models.py:298 becomes a row offset); may be NULL when p is given and na*no and the head stride are multiples
- *        of 8 (the training forward only needs p);
+ *        models.py:298 becomes a row offset); may be NULL when p is given and the head meets the tiled kernel's
+ *        conditions -- na*no and the head stride multiples of 8, `head` 16-byte aligned, 32 pixels of na*no bf16 channels within
+ *        64 KiB (na*no <= 1024), no <= 96 -- otherwise RYOLO_EINVAL (the training forward only needs p);
  *   p  [bs, na, ny, nx, no] fp32 (may be NULL): the raw head values, the "training output" of models.py:189-194.
  *   anchors [na][3] fp32 = (w_px, h_px, angle_rad) (utils/parse_config.py:6-31 rows selected by the yolo mask);
  *   stride = img_size / grid (model_utils.py:20); context_factor = hyp['context_factor'] (models.py:207-208);
- *   arc: 0 'default*' (sigmoid obj+cls), 1 '*BCE*', 2 '*CE*' (models.py:210-218).
+ *   arc: 0 'default*' (sigmoid obj+cls), 1 '*BCE*' (sigmoid cls, obj = 1), 2 '*CE*' (models.py:210-218).  The reference's CE line
+ *        assigns nc+2 softmax values to nc+1 columns and raises; the definition is the torch backend's (rotate-yolov3_amd/model/models.py,
+ *        YOLOLayer.forward): cls = softmax over [obj, cls...] without its first entry, obj = 1.  nc == 1 sets the class column to 1 last.
  */
 int ryolo_yolo_decode(const void *head, int head_cstride, int bs, int ny, int nx, int na, int no,
                       const float *anchors, float stride, float context_factor, int arc, float *io,
@@ -283,7 +286,9 @@ int ryolo_conv_head_decode_store(const ryolo_conv_desc *desc, const void *x, con
                                  int na, int no, void *head, int head_cstride, float *p, void *stream);
 
 /* NHWC bf16 helpers for cfg graphs whose shortcut / upsample / route / maxpool cannot be fused into a conv
- * epilogue (model/models.py:79-94, :269-282).  Channel counts and strides multiples of 8. */
+ * epilogue (model/models.py:79-94, :269-282).  Channel counts and strides multiples of 8.
+ * ryolo_add_nhwc: y = bf16(float(a) + float(b)); y may alias a or b exactly (same pointer, same stride: each element is read by the
+ * one thread that then writes it), which the training engine uses to accumulate in place; partially overlapping tensors are not allowed. */
 int ryolo_add_nhwc(const void *a, int a_cstride, const void *b, int b_cstride, void *y, int y_cstride,
                    long long npix, int C, void *stream);
 int ryolo_upsample_nhwc(const void *x, int x_cstride, void *y, int y_cstride, int N, int H, int W, int C, int scale,

@@ -3,6 +3,7 @@ Python (tests/golden/gen_model_golden.py)."""
 import os
 
 import numpy as np
+import pytest
 import torch
 
 import rotate_yolov3_amd  # noqa: F401
@@ -49,6 +50,36 @@ def test_decode_matches_reference():
     io, p5 = do.decode(torch.from_numpy(z["head"]), z["anchors"], (128, 128))
     assert np.allclose(io.numpy(), z["io"], rtol=1e-6, atol=1e-6)
     assert np.array_equal(p5.numpy(), z["p"])
+
+
+@pytest.mark.parametrize("cf", [1.0, 1.25])
+@pytest.mark.parametrize("nc", [1, 3])
+@pytest.mark.parametrize("arc", ["default", "uBCE", "uCE"])
+def test_decode_equals_the_torch_backend_yolo_layer_for_every_arc(arc, nc, cf):
+    """oracle decode vs YOLOLayer.forward of the product's torch backend on the CPU: the two statements of every arc's decode (the CE
+    one is the product's own definition, see the oracle's comment) agree; float64 evaluation stays within fp32 rounding of it"""
+    from rotate_yolov3_amd.model.models import YOLOLayer
+    na, ny, nx = 4, 5, 7
+    no = nc + 6
+    g = torch.Generator().manual_seed(7 + nc)
+    head = torch.randn(2, na * no, ny, nx, generator=g) * 1.5
+    anchors = np.array([[30., 10., -0.6], [12., 40., 0.6], [60., 20., -1.2], [90., 30., 0.0]])
+    img = (ny * 16, nx * 16)
+    layer = YOLOLayer(anchors=anchors, nc=nc, yolo_index=0, arc=arc, hyp={"context_factor": cf}).eval()
+    with torch.no_grad():
+        io_t, p_t = layer(head.clone(), img)
+    io, p5 = do.decode(head.clone(), anchors, img, cf=cf, arc=arc, nc=nc)
+    assert io.dtype == torch.float32 and torch.equal(p5, p_t)
+    assert io.shape == io_t.shape and np.allclose(io.numpy(), io_t.numpy(), rtol=1e-6, atol=1e-6)
+    io64, p64 = do.decode(head.clone(), anchors, img, cf=cf, arc=arc, nc=nc, dtype=torch.float64)
+    assert io64.dtype == torch.float64 and torch.equal(p64, p_t)
+    assert np.allclose(io64.numpy(), io_t.double().numpy(), rtol=2e-5, atol=2e-5)     # the decode bar of tests/test_model_gpu.py
+    # what tells the arcs apart
+    if arc != "default":
+        assert bool((io[..., 5] == 1).all())
+    if arc == "uCE" and nc > 1:
+        s = io[..., 6:].sum(-1)
+        assert bool((s < 1).all()) and bool((s > 0).all())      # the background's share is left out
 
 
 def _check_forward(fix, cfg_text):

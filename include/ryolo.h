@@ -232,6 +232,37 @@ int ryolo_conv_wgrad_kernel_choice(const ryolo_conv_desc *forward_desc);
 int ryolo_conv2d_dilated_supported(const ryolo_conv_desc *desc, int dil_h, int dil_w);
 int ryolo_conv2d_dilated(const ryolo_conv_desc *desc, int dil_h, int dil_w, const void *x, const void *w_packed, const float *scale,
                          const float *shift, const void *residual /* may be NULL */, void *y, void *stream);
+/* Data gradient of that dilated convolution (training, csrc/conv_dil.hip) -- replaces what autograd computes for the F.conv2d of a
+ * `d-convolutional` block with `weight_from` (model/models.py:254-267) with respect to its input:
+ *     dx[n,h,w,ci] = sum_{r,s,co} dz[n, h-(r-1)*dil_h, w-(s-1)*dil_w, co] * W[co,ci,r,s],
+ * the same dilated convolution applied to dz with the spatially flipped, channel-transposed filter, on the same kernel.  forward_desc
+ * describes the FORWARD conv (dx has its input's geometry and pixel stride in_cstride); the calling convention is ryolo_conv2d_dgrad's
+ * without `accumulate`: dz NHWC bf16 with pixel stride dz_cstride, ones / zeros fp32 [ryolo_conv_cpad(Cin)].  packed_dgrad is the
+ * stride-1 image of ryolo_conv_pack_weights_dgrad for the source layer's weight, which for the served shapes is bit-equal to
+ * ryolo_conv_pack_weights applied to W.flip(2,3).transpose(0,1): one packed copy serves the source layer's own data gradient and every
+ * sharer's.  Served (ryolo_conv2d_dilated_dgrad_supported, no device call; dz's stride taken as out_cstride): the forward is served and
+ * Cout % 64 == 0 (it is the K channel count here), Cin % 8 == 0.  Anything else: RYOLO_EINVAL before any HIP call.  dx is written once:
+ * one writer per element and a fixed summation order, bit-identical from run to run and independent of the batch size. */
+int ryolo_conv2d_dilated_dgrad_supported(const ryolo_conv_desc *forward_desc, int dil_h, int dil_w);
+int ryolo_conv2d_dilated_dgrad(const ryolo_conv_desc *forward_desc, int dil_h, int dil_w, const void *dz, int dz_cstride,
+                               const void *packed_dgrad, const float *ones, const float *zeros /* fp32 [cpad(Cin)] */, void *dx,
+                               void *stream);
+/* Weight gradient of the dilated convolution (training, csrc/wgrad_dil.hip) -- autograd's gradient of the same F.conv2d with respect to
+ * the shared weight:
+ *     dW[co,ci,r,s] (+)= sum_{n,h,w} dz[n,h,w,co] * x[n, h+(r-1)*dil_h, w+(s-1)*dil_w, ci],   zero outside the image.
+ * x (pixel stride forward_desc->in_cstride) and dz (pixel stride dz_cstride) are NHWC bf16, possibly channel slices; grad_oihw is the fp32
+ * [Cout][Cin][3][3] gradient.  MFMA over the pixels, split over pixel chunks into fp32 partial tiles in `workspace`
+ * (ryolo_conv2d_dilated_wgrad_workspace_bytes; any contents on entry), reduced by one launch in a fixed order: no atomics, results are
+ * bit-identical from run to run; the split count depends on the shape alone.  accumulate = 0 overwrites grad_oihw, accumulate = 1 adds:
+ * the sharers of one source weight accumulate into it in launch order.  Served (ryolo_conv2d_dilated_wgrad_supported, no device call;
+ * dz's stride taken as out_cstride): ksize 3, stride 1, pad 1, upsample 1, Cin % 64 == 0, Cout % 8 == 0 (a ragged last C_out tile: the
+ * rows past Cout are not stored), 1 <= dil_h, dil_w <= 32, channel strides multiples of 8 and at least the channel counts, x / dz /
+ * workspace 16-byte aligned, tensors below 2 GiB.  Anything else (a short workspace, a null pointer): RYOLO_EINVAL before any HIP call;
+ * the workspace query returns 0.  `tile`, `act` are ignored.  Only enqueues on `stream`, allocates nothing. */
+int ryolo_conv2d_dilated_wgrad_supported(const ryolo_conv_desc *forward_desc, int dil_h, int dil_w);
+size_t ryolo_conv2d_dilated_wgrad_workspace_bytes(const ryolo_conv_desc *forward_desc, int dil_h, int dil_w);
+int ryolo_conv2d_dilated_wgrad(const ryolo_conv_desc *forward_desc, int dil_h, int dil_w, const void *x, const void *dz, int dz_cstride,
+                               float *grad_oihw, int accumulate, void *workspace, size_t workspace_bytes, void *stream);
 /* layout converters at the model boundary: the reference feeds NCHW fp32 images (train.py:236, detect.py:209) */
 int ryolo_nchw_f32_to_nhwc_bf16(const float *x, int N, int C, int H, int W, int Cpad, void *y, void *stream);
 int ryolo_nhwc_bf16_to_nchw_f32(const void *x, int N, int C, int H, int W, int cstride, float *y, void *stream);

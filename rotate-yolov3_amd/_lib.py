@@ -46,6 +46,12 @@ _sigs = {
     "ryolo_conv_head_decode_supported": (C.c_int, [_dp, C.c_int, C.c_int]),
     "ryolo_conv0_recompute_supported": (C.c_int, [_dp]),
     "ryolo_conv2d_dgrad_bnreduce_rows": (C.c_int, [_dp]),
+    # gradients of the dilated shared 3x3 conv (csrc/conv_dil.hip, csrc/wgrad_dil.hip); the *_supported / workspace queries make no device call
+    "ryolo_conv2d_dilated_dgrad_supported": (C.c_int, [_dp, C.c_int, C.c_int]),
+    "ryolo_conv2d_dilated_dgrad": (C.c_int, [_dp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "ryolo_conv2d_dilated_wgrad_supported": (C.c_int, [_dp, C.c_int, C.c_int]),
+    "ryolo_conv2d_dilated_wgrad_workspace_bytes": (C.c_size_t, [_dp, C.c_int, C.c_int]),
+    "ryolo_conv2d_dilated_wgrad": (C.c_int, [_dp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp]),
     # squeeze-and-excitation (csrc/se.hip)
     "ryolo_se_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ryolo_se_nhwc": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp]),

@@ -252,9 +252,50 @@ bool dil_params(const ryolo_conv_desc *d, int dil_h, int dil_w, DilParams &p) {
            buffer_extent((d->Cout + 127) / 128 * 128, p.Kpad, p.Kpad + 128, &p.w_bytes);
 }
 
+// The data gradient of the forward conv `f`: dx[n,h,w,ci] = sum_{r,s,co} dy[n, h-(r-1)*dh, w-(s-1)*dw, co] * W[co,ci,r,s] is the same dilated
+// convolution applied to dy with the spatially flipped, channel-transposed filter and the same dilation -- the kernel above on a descriptor
+// with the channel counts swapped, the packed image of W'[ci][co][r][s] = W[co][ci][2-r][2-s] (for these shapes exactly the stride-1 image
+// of ryolo_conv_pack_weights_dgrad), scale 1, shift 0, linear.  Served when the forward is and C_out (the K channel count here) % 64 == 0.
+bool dil_dgrad_params(const ryolo_conv_desc *f, int dil_h, int dil_w, int dz_cstride, DilParams &p) {
+    DilParams fwd{};
+    if (!dil_params(f, dil_h, dil_w, fwd) || (f->Cout % BK) || (f->Cin & 7)) return false;
+    ryolo_conv_desc g = *f;
+    g.Cin = f->Cout; g.Cout = f->Cin;
+    g.in_cstride = dz_cstride; g.out_cstride = f->in_cstride; g.res_cstride = 0;
+    g.act = RYOLO_ACT_LINEAR;
+    return dil_params(&g, dil_h, dil_w, p);
+}
+
+// the 128 x 128 tile when its tile list gives every CU a workgroup, else the 64 x 64 tile (four times the workgroups)
+int launch_dil_auto(DilParams &p, hipStream_t stream) {
+    const long long big = ((long long)p.M + 127) / 128 * ((p.Cout + 127) / 128);
+    if (big >= cu_count()) return launch_dil<128, 128>(p, stream);
+    return launch_dil<64, 64>(p, stream);
+}
+
 }  // namespace
 
 extern "C" {
+
+int ryolo_conv2d_dilated_dgrad_supported(const ryolo_conv_desc *f, int dil_h, int dil_w) {
+    DilParams p{};
+    return f && dil_dgrad_params(f, dil_h, dil_w, f->out_cstride, p) ? 1 : 0;
+}
+
+int ryolo_conv2d_dilated_dgrad(const ryolo_conv_desc *f /* the FORWARD conv */, int dil_h, int dil_w, const void *dz, int dz_cstride,
+                               const void *packed_dgrad, const float *ones, const float *zeros, void *dx, void *stream) {
+    if (!f || !dz || !packed_dgrad || !ones || !zeros || !dx) return RYOLO_EINVAL;
+    if (((uintptr_t)dz | (uintptr_t)dx | (uintptr_t)packed_dgrad | (uintptr_t)ones | (uintptr_t)zeros) & 15) return RYOLO_EINVAL;
+    DilParams p{};
+    if (!dil_dgrad_params(f, dil_h, dil_w, dz_cstride, p)) return RYOLO_EINVAL;
+    p.x = (const __bf16 *)dz;
+    p.w = (const __bf16 *)packed_dgrad;
+    p.scale = ones;
+    p.shift = zeros;
+    p.res = nullptr;
+    p.y = (__bf16 *)dx;
+    return launch_dil_auto(p, (hipStream_t)stream);
+}
 
 int ryolo_conv2d_dilated_supported(const ryolo_conv_desc *d, int dil_h, int dil_w) {
     DilParams p{};
@@ -274,10 +315,7 @@ int ryolo_conv2d_dilated(const ryolo_conv_desc *d, int dil_h, int dil_w, const v
     p.shift = shift;
     p.res = (const __bf16 *)residual;
     p.y = (__bf16 *)y;
-    // the 128 x 128 tile when its tile list gives every CU a workgroup, else the 64 x 64 tile (four times the workgroups)
-    const long long big = ((long long)p.M + 127) / 128 * ((p.Cout + 127) / 128);
-    if (big >= cu_count()) return launch_dil<128, 128>(p, (hipStream_t)stream);
-    return launch_dil<64, 64>(p, (hipStream_t)stream);
+    return launch_dil_auto(p, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -89,6 +89,12 @@ def conv2d_bn_act(x, packed_w, scale, shift, cout, ksize, stride=1, pad=None, ac
     return out
 
 
+def conv2d_dilated_supported(d, dil):
+    """does csrc/conv_dil.hip serve the dilated 3x3 conv of descriptor d (no device call)"""
+    dh, dw = (dil, dil) if isinstance(dil, int) else dil
+    return bool(_lib.lib().ryolo_conv2d_dilated_supported(C.byref(d), int(dh), int(dw)))
+
+
 def conv2d_dilated(x, packed_w, scale, shift, cout, dil, act=ACT_LINEAR, slope=0.1, residual=None, out=None):
     """y = act(conv3x3(x, W, padding=dil, dilation=dil) * scale + shift) + residual (csrc/conv_dil.hip); dil = (dh, dw); packed_w is the
     image pack_weights makes for the undilated 3x3 layer; x, residual, out: NHWC bf16 (possibly slices), the output is H x W."""

@@ -1,11 +1,13 @@
-"""Python handles on the training-step entry points of the C ABI (include/ryolo.h; csrc/train.hip, csrc/wgrad.hip, csrc/conv_dgrad.hip + csrc/conv.hip).
+"""Python handles on the training-step entry points of the C ABI (include/ryolo.h; csrc/train.hip, csrc/wgrad.hip, csrc/conv_dgrad.hip + csrc/conv.hip;
+csrc/conv_dil.hip + csrc/wgrad_dil.hip for the dilated shared convs of the matrix cfgs).
 Plumbing only: torch owns the device memory and the stream."""
 import ctypes as C
 
 import torch
 
 from .. import _lib
-from .hip_ops import ConvDesc, _check_nhwc, cpad
+from . import hip_ops
+from .hip_ops import ConvDesc, _check_nhwc, cpad, pack_weights
 
 _vp = C.c_void_p
 _P = C.POINTER(ConvDesc)
@@ -398,6 +400,122 @@ def conv_wgrad_partials(d, x, dz, cin_real, grad, accumulate, ws):
     _lib.check(_lib.lib().ryolo_conv2d_wgrad_partials(C.byref(d), x.data_ptr(), dz.data_ptr(), dz.stride(2), cin_real, grad.data_ptr(),
                                                       1 if accumulate else 0, ws.data_ptr(), ws.numel(), _s(x.device)),
                "ryolo_conv2d_wgrad_partials")
+
+
+# ---- the dilated shared 3x3 conv of the matrix cfgs (signatures: _lib.py)
+def _dil(dil):
+    dh, dw = (dil, dil) if isinstance(dil, int) else dil
+    return int(dh), int(dw)
+
+
+def dilated_desc(n, h, w, cin, cout, in_cs=None, out_cs=None):
+    """the forward descriptor of a dilated 3x3 / stride 1 conv (include/ryolo.h: ksize 3, pad 1 names the undilated window)"""
+    return ConvDesc(n, h, w, cin, cout, 3, 1, 1, in_cs or cin, out_cs or cout, 0, 0, 0.0, 1, 0)
+
+
+def conv_dilated_dgrad_supported(d, dil):
+    return bool(_lib.lib().ryolo_conv2d_dilated_dgrad_supported(C.byref(d), *_dil(dil)))
+
+
+def conv_dilated_wgrad_supported(d, dil):
+    return bool(_lib.lib().ryolo_conv2d_dilated_wgrad_supported(C.byref(d), *_dil(dil)))
+
+
+def conv_dilated_wgrad_ws_bytes(d, dil):
+    return _lib.lib().ryolo_conv2d_dilated_wgrad_workspace_bytes(C.byref(d), *_dil(dil))
+
+
+def conv_dilated_dgrad(d, dil, dz, packed_dgrad, ones, zeros, dx):
+    """dx = conv3x3(dz, flipped / transposed W, padding=dil, dilation=dil) for the FORWARD conv `d` (csrc/conv_dil.hip); packed_dgrad: the
+    stride-1 image of pack_weights_dgrad for the shared weight; ones / zeros: fp32 [cpad(Cin)]"""
+    _check_nhwc(dz, "dz")
+    _check_nhwc(dx, "dx")
+    dh, dw = _dil(dil)
+    with torch.cuda.device(dz.device):
+        rc = _lib.lib().ryolo_conv2d_dilated_dgrad(C.byref(d), dh, dw, dz.data_ptr(), dz.stride(2), packed_dgrad.data_ptr(), ones.data_ptr(),
+                                                   zeros.data_ptr(), dx.data_ptr(), _s(dz.device))
+    _lib.check(rc, "ryolo_conv2d_dilated_dgrad")
+
+
+def conv_dilated_wgrad(d, dil, x, dz, grad, accumulate, ws):
+    """grad (fp32 OIHW) (+)= the weight gradient of the dilated conv `d` (csrc/wgrad_dil.hip); ws: uint8, >= conv_dilated_wgrad_ws_bytes"""
+    _check_nhwc(x, "x")
+    _check_nhwc(dz, "dz")
+    dh, dw = _dil(dil)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().ryolo_conv2d_dilated_wgrad(C.byref(d), dh, dw, x.data_ptr(), dz.data_ptr(), dz.stride(2), grad.data_ptr(),
+                                                   1 if accumulate else 0, ws.data_ptr(), ws.numel() * ws.element_size(), _s(x.device))
+    _lib.check(rc, "ryolo_conv2d_dilated_wgrad")
+
+
+class SharedConvPacks(object):
+    """The packed images of the shared source weights of one model, forward and data-gradient, keyed on the weight's (data_ptr, _version):
+    the sharers of a source pack it once per direction per optimizer step (an in-place update bumps the version).  Also holds the per-channel
+    ones / zeros vectors the kernels' epilogue reads.  Lives on the model (Darknet.shared_conv_packs)."""
+
+    def __init__(self):
+        self._fwd, self._dgrad, self._vec = {}, {}, {}
+
+    @staticmethod
+    def _get(table, weight, pack):
+        ent = table.get(weight.data_ptr())
+        if ent is None or ent[0] != weight._version:
+            ent = (weight._version, pack(weight))
+            table[weight.data_ptr()] = ent
+        return ent[1]
+
+    def forward_image(self, weight):
+        return self._get(self._fwd, weight, lambda w: pack_weights(w.detach()))
+
+    def dgrad_image(self, weight):
+        return self._get(self._dgrad, weight, lambda w: pack_weights_dgrad(w.detach(), 1))
+
+    def vectors(self, c, device):
+        """(ones, zeros) fp32 [cpad(c)]"""
+        key = (cpad(c), device.index)
+        v = self._vec.get(key)
+        if v is None:
+            v = (torch.ones(key[0], dtype=torch.float32, device=device), torch.zeros(key[0], dtype=torch.float32, device=device))
+            self._vec[key] = v
+        return v
+
+
+class SharedDilatedConv(torch.autograd.Function):
+    """y = F.conv2d(x, weight, padding=dil, dilation=dil) for a d-convolutional block with weight_from (model/models.py:254-267) on the HIP
+    kernels, inside an ATen chain: x NCHW fp32 -> NHWC bf16, ryolo_conv2d_dilated (scale 1, shift 0, linear), -> NCHW fp32.  Saves the bf16
+    NHWC x, not the fp32 input.  Backward: dy -> NHWC bf16; the data gradient only when the input needs one; the weight gradient into a
+    fresh fp32 OIHW tensor that is returned -- autograd sums the sharers.  apply(x, weight, dil[, packs]): packs = the model's
+    SharedConvPacks (None: pack for this call)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, dil, packs=None):
+        packs = packs if packs is not None else SharedConvPacks()
+        cout, cin = weight.shape[0], weight.shape[1]
+        xb = hip_ops.nchw_f32_to_nhwc_bf16(x)
+        ones, zeros = packs.vectors(cout, x.device)
+        yb = hip_ops.conv2d_dilated(xb, packs.forward_image(weight), ones, zeros, cout, dil)
+        ctx.save_for_backward(xb, weight)
+        ctx.dil, ctx.packs = _dil(dil), packs
+        return hip_ops.nhwc_bf16_to_nchw_f32(yb)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xb, weight = ctx.saved_tensors
+        n, h, w, cin = xb.shape
+        cout = weight.shape[0]
+        d = dilated_desc(n, h, w, cin, cout)
+        dyb = hip_ops.nchw_f32_to_nhwc_bf16(dy.float())
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            ones, zeros = ctx.packs.vectors(cin, dy.device)
+            dxb = torch.empty((n, h, w, cin), dtype=torch.bfloat16, device=dy.device)
+            conv_dilated_dgrad(d, ctx.dil, dyb, ctx.packs.dgrad_image(weight), ones, zeros, dxb)
+            dx = hip_ops.nhwc_bf16_to_nchw_f32(dxb)
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty(weight.shape, dtype=torch.float32, device=dy.device)
+            ws = torch.empty(conv_dilated_wgrad_ws_bytes(d, ctx.dil), dtype=torch.uint8, device=dy.device)
+            conv_dilated_wgrad(d, ctx.dil, xb, dyb, dw, False, ws)
+        return dx, dw, None, None
 
 
 def upsample2x_bwd(dy, dx, accumulate):

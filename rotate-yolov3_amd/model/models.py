@@ -269,7 +269,36 @@ class Darknet(nn.Module):
         self.version = np.array([0, 2, 5], dtype=np.int32)
         self.seen = np.array([0], dtype=np.int64)
         self.backend = 'hip'      # 'hip' (eval + GPU) | 'torch' (explicit request for the ATen chain on any device)
+        self.shared_conv_backend = 'torch'   # the d-convolutional weight_from layers of _torch_forward on CUDA tensors: 'torch' | 'hip'
         self._engines = {}
+
+    @property
+    def shared_conv_backend(self):
+        """What _torch_forward runs the dilated 3x3 `d-convolutional` layers with `weight_from` on, for CUDA tensors: 'torch' (F.conv2d and
+        autograd's backward) or 'hip' (hip_train_ops.SharedDilatedConv: csrc/conv_dil.hip forward and data gradient, csrc/wgrad_dil.hip
+        weight gradient, bf16 operands).  Read by _torch_forward only; CPU tensors ignore it."""
+        return self.__dict__.get('_shared_conv_backend', 'torch')      # (a model unpickled from before the attribute existed: the default)
+
+    @shared_conv_backend.setter
+    def shared_conv_backend(self, value):
+        if value not in ('torch', 'hip'):
+            raise ValueError("shared_conv_backend must be 'torch' or 'hip', not %r" % (value,))
+        self._shared_conv_backend = value
+
+    def _shared_dilated_conv(self, i, mdef, x, weight, dil):
+        """layer i (d-convolutional, weight_from) through SharedDilatedConv; an unsupported layer is an error, never a fallback"""
+        from . import hip_ops, hip_train_ops as T
+        n, cin, h, w = x.shape
+        d = T.dilated_desc(n, h, w, cin, weight.shape[0])
+        k, pad, _ = shared_conv_geometry(mdef)
+        if not (k == 3 and tuple(pad) == tuple(dil) and hip_ops.conv2d_dilated_supported(d, dil) and T.conv_dilated_dgrad_supported(d, dil)
+                and T.conv_dilated_wgrad_supported(d, dil)):
+            raise RuntimeError("layer %d (d-convolutional, weight_from = %s): shared_conv_backend = 'hip' does not serve %d -> %d channels, "
+                               "size %d, pad %s, dilation %s" % (i, mdef['weight_from'], cin, weight.shape[0], k, tuple(pad), tuple(dil)))
+        packs = self.__dict__.get('shared_conv_packs')
+        if packs is None:
+            packs = self.shared_conv_packs = T.SharedConvPacks()
+        return T.SharedDilatedConv.apply(x, weight, tuple(dil), packs)
 
     # ------------------------------------------------------------------ ATen operator chain (reference CPU path)
     def _torch_forward(self, x):
@@ -280,7 +309,11 @@ class Darknet(nn.Module):
             mtype = mdef['type']
             if 'weight_from' in mdef:      # convolutional / d-convolutional sharing a weight: no bias, BatchNorm or activation
                 _, pad, dil = shared_conv_geometry(mdef)
-                x = F.conv2d(x, self.module_list[int(mdef['weight_from'])].Conv2d.weight, padding=pad, dilation=dil)
+                weight = self.module_list[int(mdef['weight_from'])].Conv2d.weight
+                if mtype == 'd-convolutional' and x.is_cuda and self.shared_conv_backend == 'hip':
+                    x = self._shared_dilated_conv(i, mdef, x, weight, dil)
+                else:
+                    x = F.conv2d(x, weight, padding=pad, dilation=dil)
             elif mtype in ['convolutional', 'upsample', 'maxpool', 'se']:
                 x = module(x)
             elif mtype == 'route':

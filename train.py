@@ -10,7 +10,9 @@ train.py ...`) with bucketed RCCL all-reduce overlapped with backward (rotate-yo
 reference's broken single-process DDP; the input pipeline is synthetic (`--synthetic N` images per epoch) because the
 OpenCV/imgaug loader is out of scope.  On a GPU the training-mode forward AND backward run the hand-written HIP
 TrainEngine (conv forward / dgrad / wgrad on MFMA, BatchNorm + PReLU kernels, fused loss, one-launch SGD;
-rotate-yolov3_amd/model/train_engine.py); CPU tensors and `model.backend = 'torch'` take the ATen operator chain.
+rotate-yolov3_amd/model/train_engine.py); CPU tensors and `--backend torch` (model.backend = 'torch') take the ATen operator chain --
+the way to train a "matrix" cfg (weight_from / d-convolutional layers), which the TrainEngine refuses; `--shared-conv hip` then runs
+its dilated shared 3x3 layers on the HIP kernels (model.shared_conv_backend, hip_train_ops.SharedDilatedConv).
 Per-epoch evaluation follows the reference's gate (train.py:306-314: test.test(model=model) every `test_interval`
 epochs from epoch 10 on, always considered at the final epoch unless --notest), `last.pt` is written every epoch and
 `best.pt` when the mAP fitness does not decrease (train.py:345-357).
@@ -102,7 +104,9 @@ def train(opt, hyp):
 
     model = Darknet(opt.cfg, hyp, arc=opt.arc).to(device)
     model.nc, model.arc, model.hyp = nc, opt.arc, hyp
-    if use_cuda and not opt.eager_loss:
+    model.backend = getattr(opt, 'backend', 'hip')
+    model.shared_conv_backend = getattr(opt, 'shared_conv', 'torch')
+    if use_cuda and not opt.eager_loss and model.backend == 'hip':      # (the graph-captured loss reads the TrainEngine's heads)
         model.enable_fused_loss(capacity=max(256, 8 * batch_size))   # compute_loss as one hipGraph replay (loss_static.py)
     optimizer = make_optimizer(model, hyp, opt.adam)
     start_epoch, best_fitness = 0, 0.
@@ -195,8 +199,8 @@ def train(opt, hyp):
     return results
 
 
-if __name__ == '__main__':
-    from rotate_yolov3_amd.utils.cli import add_ignored, report_ignored
+def make_parser():
+    from rotate_yolov3_amd.utils.cli import add_ignored
     parser = argparse.ArgumentParser()                                   # the reference's flags (train.py:383-404), same defaults
     parser.add_argument('--accumulate', type=int, default=1, help='batches to accumulate before optimizing')
     parser.add_argument('--hyp', type=str, default='cfg/HRSC/hyp.py', help='hyper-parameter path')
@@ -220,6 +224,12 @@ if __name__ == '__main__':
     parser.add_argument('--synthetic', type=int, default=64, help='synthetic images per epoch per process')
     parser.add_argument('--bucket-mb', type=float, default=64.0, help='gradient all-reduce bucket size')
     parser.add_argument('--eager-loss', action='store_true', help='eager compute_loss mirror instead of the graph-captured loss')
+    parser.add_argument('--backend', choices=['hip', 'torch'], default='hip',
+                        help="model.backend: 'hip' trains on the HIP TrainEngine, 'torch' on the ATen operator chain (the matrix cfgs with "
+                             "weight_from / d-convolutional layers, which the TrainEngine refuses)")
+    parser.add_argument('--shared-conv', choices=['torch', 'hip'], default='torch',
+                        help="model.shared_conv_backend: with --backend torch, run the dilated weight_from layers of a matrix cfg on the HIP "
+                             "kernels ('hip') or on F.conv2d ('torch')")
     ignored = add_ignored(parser, [
         ('--multi-scale', dict(action='store_true', help='adjust (67%% - 150%%) img_size every 10 batches (the engine plans one input shape)')),
         ('--rect', dict(action='store_true', help='rectangular training (an image-loader mode)')),
@@ -230,7 +240,20 @@ if __name__ == '__main__':
         ('--img-weights', dict(action='store_true', help='select training images by weight')),
         ('--cache-images', dict(action='store_true', help='cache images for faster training')),
         ('--var', dict(type=float, default=None, help='debug variable'))])
-    opt = parser.parse_args()
+    return parser, ignored
+
+
+def parse_args(argv=None):
+    parser, ignored = make_parser()
+    opt = parser.parse_args(argv)
+    if opt.shared_conv == 'hip' and opt.backend == 'hip':
+        parser.error("--shared-conv hip needs --backend torch: the HIP TrainEngine refuses cfgs with weight_from / d-convolutional layers")
+    return parser, ignored, opt
+
+
+if __name__ == '__main__':
+    from rotate_yolov3_amd.utils.cli import report_ignored
+    parser, ignored, opt = parse_args()
     if opt.resume:
         opt.weights = os.path.join(opt.wdir, 'last.pt')          # reference train.py:406
     print(opt)

@@ -346,6 +346,32 @@ size_t ryolo_se_workspace_bytes(int N, int H, int W, int C);
 int ryolo_se_nhwc(const void *x, int x_cstride, const float *w1 /* fp32 [hidden][C] */, const float *w2 /* fp32 [C][hidden] */,
                   int hidden, void *y, int y_cstride, int N, int H, int W, int C,
                   float *gate_out /* fp32 [N][C], may be NULL */, void *workspace, size_t workspace_bytes, void *stream);
+/* Backward of that block (training, csrc/se_bwd.hip) -- replaces what autograd computes for SELayer.forward.  Saved from the forward: x
+ * and the two weights; the gate is recomputed, by the forward's code in the forward's order (gate_out here is bit-equal to ryolo_se_nhwc's
+ * on the same x).  Given dy (NHWC bf16), with m, u = W1 . m, z = relu(u), g as above; every sum and product fp32 on the bf16 values:
+ *     s[n,c]  = sum_hw dy * x                       dt = s * g * (1 - g)
+ *     dW2[c,h] (+)= sum_n dt[n,c] * z[n,h]          dz[n,h] = sum_c dt[n,c] * W2[c,h]     du = dz where z > 0, else 0
+ *     dW1[h,c] (+)= sum_n du[n,h] * m[n,c]          dm[n,c] = sum_h du[n,h] * W1[h,c]
+ *     dx = bf16(float(dy) * g + dm / (H*W))         one rounding; dx_accumulate = 1 adds float(dx's old value) before that rounding
+ *   x, dy, dx   NHWC bf16 [N, H, W, C], each possibly a channel slice (`*_cstride` >= C, a multiple of 8, base 16-byte aligned).  dx may be
+ *               NULL: no data gradient.  dx must overlap neither x nor dy, by ryolo_se_nhwc's rule (two disjoint channel slices of one
+ *               buffer do not overlap).
+ *   dw1, dw2    fp32 [hidden][C] / [C][hidden]; both NULL: no weight gradients (one alone NULL: RYOLO_EINVAL).  accumulate_w = 0 overwrites
+ *               them (any contents on entry), 1 adds the batch's sum to the old value with one fp32 add per element.
+ *   gate_out    fp32 [N][C] (may be NULL): receives g.
+ *   workspace   ryolo_se_bwd_workspace_bytes(N, H, W, C, hidden) bytes of device scratch, 16-byte aligned (contents irrelevant on entry).
+ * At most four launches on `stream` (pixel sums of x and dy * x per chunk; gate and the per-image vectors; weight gradients, when wanted;
+ * dx, when wanted); nothing is allocated.  The chunking depends on (H, W, C) alone, the sums over chunks, channels, hidden units and
+ * images run in a fixed order and there are no atomics: every output is bit-identical from run to run, and dx / gate_out of an image do
+ * not depend on the batch it is in.  Served: ryolo_se_nhwc's range (C % 8 == 0, 16 <= C <= 2048, 1 <= hidden <= 128, N <= 65535).
+ * RYOLO_EINVAL, before anything is enqueued: a null x / dy / w1 / w2 / workspace, dx and both dw* all NULL, a size outside the range, a
+ * misaligned pointer or stride, workspace_bytes below the reported size, dx overlapping x or dy.  The workspace query returns 0 for a shape
+ * that is not served. */
+size_t ryolo_se_bwd_workspace_bytes(int N, int H, int W, int C, int hidden);
+int ryolo_se_bwd_nhwc(const void *x, int x_cstride, const void *dy, int dy_cstride, const float *w1 /* fp32 [hidden][C] */,
+                      const float *w2 /* fp32 [C][hidden] */, int hidden, void *dx /* may be NULL */, int dx_cstride, int dx_accumulate,
+                      float *dw1, float *dw2 /* both may be NULL */, int accumulate_w, int N, int H, int W, int C,
+                      float *gate_out /* fp32 [N][C], may be NULL */, void *workspace, size_t workspace_bytes, void *stream);
 
 
 /* ------------------------------------------------------------------------------------------------

@@ -55,6 +55,10 @@ _sigs = {
     # squeeze-and-excitation (csrc/se.hip)
     "ryolo_se_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ryolo_se_nhwc": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp]),
+    # its backward (csrc/se_bwd.hip)
+    "ryolo_se_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ryolo_se_bwd_nhwc": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp]),
 }
 
 

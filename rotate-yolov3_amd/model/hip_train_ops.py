@@ -1,5 +1,5 @@
 """Python handles on the training-step entry points of the C ABI (include/ryolo.h; csrc/train.hip, csrc/wgrad.hip, csrc/conv_dgrad.hip + csrc/conv.hip;
-csrc/conv_dil.hip + csrc/wgrad_dil.hip for the dilated shared convs of the matrix cfgs).
+csrc/conv_dil.hip + csrc/wgrad_dil.hip for the dilated shared convs of the matrix cfgs; csrc/se_bwd.hip for the se blocks).
 Plumbing only: torch owns the device memory and the stream."""
 import ctypes as C
 
@@ -516,6 +516,85 @@ class SharedDilatedConv(torch.autograd.Function):
             ws = torch.empty(conv_dilated_wgrad_ws_bytes(d, ctx.dil), dtype=torch.uint8, device=dy.device)
             conv_dilated_wgrad(d, ctx.dil, xb, dyb, dw, False, ws)
         return dx, dw, None, None
+
+
+# ---- squeeze-and-excitation backward (csrc/se_bwd.hip; signatures: _lib.py)
+def se_bwd_ws_bytes(n, h, w, c, hidden):
+    """bytes of scratch of one se_bwd_nhwc call; 0: the shape is not served (no device call)"""
+    return _lib.lib().ryolo_se_bwd_workspace_bytes(int(n), int(h), int(w), int(c), int(hidden))
+
+
+def se_bwd_nhwc(x, dy, w1, w2, dx=None, dw1=None, dw2=None, dx_accumulate=False, accumulate_w=False, gate_out=None, workspace=None):
+    """The gradients of y = x * sigmoid(W2 . relu(W1 . mean_hw(x))) given dy (include/ryolo.h: ryolo_se_bwd_nhwc).  x, dy, dx: NHWC bf16
+    (possibly slices); w1 [hidden, C], w2 [C, hidden], dw1, dw2: contiguous fp32; dx None: no data gradient; dw1 and dw2 None: no weight
+    gradients; gate_out: fp32 [N, C] that receives the recomputed gates; workspace: uint8, >= se_bwd_ws_bytes (None: allocated here)."""
+    x_cs = _check_nhwc(x, "x")
+    dy_cs = _check_nhwc(dy, "dy")
+    n, h, w, c = x.shape
+    assert tuple(dy.shape) == (n, h, w, c), (tuple(dy.shape), (n, h, w, c))
+    hidden = w1.shape[0]
+    for t, shape, name in ((w1, (hidden, c), "w1"), (w2, (c, hidden), "w2"), (dw1, (hidden, c), "dw1"), (dw2, (c, hidden), "dw2"),
+                           (gate_out, (n, c), "gate_out")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise RuntimeError("%s must be a contiguous fp32 GPU tensor of shape %s" % (name, shape))
+    dx_cs = 0
+    if dx is not None:
+        dx_cs = _check_nhwc(dx, "dx")
+        assert tuple(dx.shape) == (n, h, w, c), (tuple(dx.shape), (n, h, w, c))
+    if workspace is None:
+        nbytes = se_bwd_ws_bytes(n, h, w, c, hidden)
+        if nbytes == 0:
+            raise RuntimeError("se backward: unsupported shape N %d, H %d, W %d, C %d, hidden %d (C a multiple of 8 from 16 to 2048, "
+                               "hidden from 1 to 128)" % (n, h, w, c, hidden))
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().ryolo_se_bwd_nhwc(x.data_ptr(), x_cs, dy.data_ptr(), dy_cs, w1.data_ptr(), w2.data_ptr(), hidden, ptr(dx), dx_cs,
+                                          1 if dx_accumulate else 0, ptr(dw1), ptr(dw2), 1 if accumulate_w else 0, n, h, w, c,
+                                          ptr(gate_out), workspace.data_ptr(), workspace.numel() * workspace.element_size(), _s(x.device))
+    _lib.check(rc, "ryolo_se_bwd_nhwc")
+    return dx
+
+
+def se_supported(n, h, w, c, hidden):
+    """do csrc/se.hip and csrc/se_bwd.hip serve this block (no device call)"""
+    return _lib.lib().ryolo_se_workspace_bytes(int(n), int(h), int(w), int(c)) > 0 and se_bwd_ws_bytes(n, h, w, c, hidden) > 0
+
+
+class SqueezeExcite(torch.autograd.Function):
+    """y = x * sigmoid(W2 . relu(W1 . mean_hw(x))) -- SELayer.forward (model/models.py:27-31) on the HIP kernels, inside an ATen chain:
+    x NCHW fp32 -> NHWC bf16, ryolo_se_nhwc, -> NCHW fp32.  Saves the bf16 NHWC x and the two weights, not the gate (the backward
+    recomputes it).  Backward: dy -> NHWC bf16, one ryolo_se_bwd_nhwc call -- the data gradient only when the input needs one, the weight
+    gradients only when a weight needs one -- into fresh fp32 tensors; scratch from torch's allocator per call.  apply(x, w1, w2) with
+    w1 = fc.0.weight [C/16, C], w2 = fc.2.weight [C, C/16].  A CPU tensor raises: there is no fallback."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2):
+        if not (x.is_cuda and w1.is_cuda and w2.is_cuda):
+            raise RuntimeError("SqueezeExcite runs on the HIP kernels: x, w1 and w2 must be GPU tensors")
+        if x.shape[1] % 8:
+            raise RuntimeError("SqueezeExcite: %d channels (the kernels need a multiple of 8)" % x.shape[1])
+        xb = hip_ops.nchw_f32_to_nhwc_bf16(x.float())
+        w1c, w2c = w1.detach().float().contiguous(), w2.detach().float().contiguous()
+        yb = hip_ops.se_nhwc(xb, w1c, w2c)
+        ctx.save_for_backward(xb, w1c, w2c)
+        return hip_ops.nhwc_bf16_to_nchw_f32(yb)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xb, w1, w2 = ctx.saved_tensors
+        dyb = hip_ops.nchw_f32_to_nhwc_bf16(dy.float())
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        if not (need_x or need_w):
+            return None, None, None
+        dxb = torch.empty_like(xb) if need_x else None
+        dw1 = torch.empty_like(w1) if need_w else None
+        dw2 = torch.empty_like(w2) if need_w else None
+        se_bwd_nhwc(xb, dyb, w1, w2, dx=dxb, dw1=dw1, dw2=dw2)
+        dx = hip_ops.nhwc_bf16_to_nchw_f32(dxb) if need_x else None
+        return dx, (dw1 if ctx.needs_input_grad[1] else None), (dw2 if ctx.needs_input_grad[2] else None)
 
 
 def upsample2x_bwd(dy, dx, accumulate):

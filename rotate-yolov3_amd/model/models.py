@@ -41,7 +41,8 @@ class Mish(nn.Module):
 
 class SELayer(nn.Module):
     """Squeeze-and-excitation block (models.py:16-31): same attributes, so the state_dict keys are `fc.0.weight` / `fc.2.weight`.
-    On the GPU in eval mode HipEngine runs it as ryolo_se_nhwc (csrc/se.hip); this forward is the ATen chain."""
+    On the GPU in eval mode HipEngine runs it as ryolo_se_nhwc (csrc/se.hip); this forward is the ATen chain, which _torch_forward
+    replaces by hip_train_ops.SqueezeExcite for CUDA tensors when Darknet.se_backend = 'hip'."""
 
     def __init__(self, channel, reduction=16):
         super(SELayer, self).__init__()
@@ -270,6 +271,7 @@ class Darknet(nn.Module):
         self.seen = np.array([0], dtype=np.int64)
         self.backend = 'hip'      # 'hip' (eval + GPU) | 'torch' (explicit request for the ATen chain on any device)
         self.shared_conv_backend = 'torch'   # the d-convolutional weight_from layers of _torch_forward on CUDA tensors: 'torch' | 'hip'
+        self.se_backend = 'torch'            # the se layers of _torch_forward on CUDA tensors: 'torch' | 'hip'
         self._engines = {}
 
     @property
@@ -284,6 +286,29 @@ class Darknet(nn.Module):
         if value not in ('torch', 'hip'):
             raise ValueError("shared_conv_backend must be 'torch' or 'hip', not %r" % (value,))
         self._shared_conv_backend = value
+
+    @property
+    def se_backend(self):
+        """What _torch_forward runs the `se` layers on, for CUDA tensors: 'torch' (SELayer.forward, the ATen chain, and autograd's backward)
+        or 'hip' (hip_train_ops.SqueezeExcite: csrc/se.hip forward, csrc/se_bwd.hip backward, bf16 tensors, fp32 gate).  Read by
+        _torch_forward only; CPU tensors ignore it.  The HIP TrainEngine refuses se cfgs whatever this says."""
+        return self.__dict__.get('_se_backend', 'torch')               # (a model unpickled from before the attribute existed: the default)
+
+    @se_backend.setter
+    def se_backend(self, value):
+        if value not in ('torch', 'hip'):
+            raise ValueError("se_backend must be 'torch' or 'hip', not %r" % (value,))
+        self._se_backend = value
+
+    def _squeeze_excite(self, i, module, x):
+        """layer i (se) through SqueezeExcite; an unsupported layer is an error, never a fallback"""
+        from . import hip_train_ops as T
+        n, c, h, w = x.shape
+        w1, w2 = module.fc[0].weight, module.fc[2].weight
+        if not (tuple(w1.shape) == (w1.shape[0], c) and tuple(w2.shape) == (c, w1.shape[0]) and T.se_supported(n, h, w, c, w1.shape[0])):
+            raise RuntimeError("layer %d (se): se_backend = 'hip' does not serve %d channels with %d hidden units on a %d x %d x %d batch "
+                               "(channels a multiple of 8 from 16 to 2048, 1 to 128 hidden units)" % (i, c, w1.shape[0], n, h, w))
+        return T.SqueezeExcite.apply(x, w1, w2)
 
     def _shared_dilated_conv(self, i, mdef, x, weight, dil):
         """layer i (d-convolutional, weight_from) through SharedDilatedConv; an unsupported layer is an error, never a fallback"""
@@ -314,6 +339,8 @@ class Darknet(nn.Module):
                     x = self._shared_dilated_conv(i, mdef, x, weight, dil)
                 else:
                     x = F.conv2d(x, weight, padding=pad, dilation=dil)
+            elif mtype == 'se' and x.is_cuda and self.se_backend == 'hip':
+                x = self._squeeze_excite(i, module, x)
             elif mtype in ['convolutional', 'upsample', 'maxpool', 'se']:
                 x = module(x)
             elif mtype == 'route':

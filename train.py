@@ -12,7 +12,9 @@ OpenCV/imgaug loader is out of scope.  On a GPU the training-mode forward AND ba
 TrainEngine (conv forward / dgrad / wgrad on MFMA, BatchNorm + PReLU kernels, fused loss, one-launch SGD;
 rotate-yolov3_amd/model/train_engine.py); CPU tensors and `--backend torch` (model.backend = 'torch') take the ATen operator chain --
 the way to train a "matrix" cfg (weight_from / d-convolutional layers), which the TrainEngine refuses; `--shared-conv hip` then runs
-its dilated shared 3x3 layers on the HIP kernels (model.shared_conv_backend, hip_train_ops.SharedDilatedConv).
+its dilated shared 3x3 layers on the HIP kernels (model.shared_conv_backend, hip_train_ops.SharedDilatedConv).  The se cfgs train the
+same way: `--backend torch`, and `--se hip` runs their squeeze-and-excitation layers, forward and backward, on the HIP kernels
+(model.se_backend, hip_train_ops.SqueezeExcite).
 Per-epoch evaluation follows the reference's gate (train.py:306-314: test.test(model=model) every `test_interval`
 epochs from epoch 10 on, always considered at the final epoch unless --notest), `last.pt` is written every epoch and
 `best.pt` when the mAP fitness does not decrease (train.py:345-357).
@@ -106,6 +108,7 @@ def train(opt, hyp):
     model.nc, model.arc, model.hyp = nc, opt.arc, hyp
     model.backend = getattr(opt, 'backend', 'hip')
     model.shared_conv_backend = getattr(opt, 'shared_conv', 'torch')
+    model.se_backend = getattr(opt, 'se', 'torch')
     if use_cuda and not opt.eager_loss and model.backend == 'hip':      # (the graph-captured loss reads the TrainEngine's heads)
         model.enable_fused_loss(capacity=max(256, 8 * batch_size))   # compute_loss as one hipGraph replay (loss_static.py)
     optimizer = make_optimizer(model, hyp, opt.adam)
@@ -230,6 +233,9 @@ def make_parser():
     parser.add_argument('--shared-conv', choices=['torch', 'hip'], default='torch',
                         help="model.shared_conv_backend: with --backend torch, run the dilated weight_from layers of a matrix cfg on the HIP "
                              "kernels ('hip') or on F.conv2d ('torch')")
+    parser.add_argument('--se', choices=['torch', 'hip'], default='torch',
+                        help="model.se_backend: with --backend torch, run the se layers of an se cfg on the HIP kernels, forward and "
+                             "backward ('hip'), or on the ATen chain ('torch')")
     ignored = add_ignored(parser, [
         ('--multi-scale', dict(action='store_true', help='adjust (67%% - 150%%) img_size every 10 batches (the engine plans one input shape)')),
         ('--rect', dict(action='store_true', help='rectangular training (an image-loader mode)')),
@@ -248,6 +254,8 @@ def parse_args(argv=None):
     opt = parser.parse_args(argv)
     if opt.shared_conv == 'hip' and opt.backend == 'hip':
         parser.error("--shared-conv hip needs --backend torch: the HIP TrainEngine refuses cfgs with weight_from / d-convolutional layers")
+    if opt.se == 'hip' and opt.backend == 'hip':
+        parser.error("--se hip needs --backend torch: the HIP TrainEngine refuses cfgs with se layers")
     return parser, ignored, opt
 
 

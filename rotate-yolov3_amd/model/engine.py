@@ -30,6 +30,7 @@ import torch.nn as nn
 from .. import _lib
 from . import hip_ops as ops
 from . import plan
+from .nhwc_batch import NHWC8Batch
 from .plan import _abs  # noqa: F401  (the cfg's layer-index convention, for callers that walk module_defs themselves)
 
 _vp = C.c_void_p
@@ -56,6 +57,7 @@ class HipEngine(object):
         self.want_p = want_p
         self.use_graph = use_graph
         self.graph = None
+        self.graph_layers = None     # the layers without the input converter: what an NHWC8Batch replays
         defs = model.module_defs
         mods = model.module_list
         cf = float((model.hyp or {}).get('context_factor', 1.0))
@@ -326,15 +328,27 @@ class HipEngine(object):
         return run
 
     # ------------------------------------------------------------------ run
+    def _as_input(self, x):
+        """an NHWC8Batch as it is (already the engine's input layout), anything else as a contiguous fp32 NCHW tensor"""
+        if tuple(x.shape) != (self.bs, x.shape[1], self.H, self.W) or x.shape[1] > 8:
+            raise RuntimeError("engine was planned for input %s" % ((self.bs, x.shape[1], self.H, self.W),))
+        return x if isinstance(x, NHWC8Batch) else x.float().contiguous()
+
     def _launch_input(self, x):
+        if isinstance(x, NHWC8Batch):       # no converter pass: a device-to-device copy, or nothing when the batch IS the input buffer
+            x.copy_into(self.x_nhwc)
+            return
         n, c, h, w = x.shape
         _lib.check(_lib.lib().ryolo_nchw_f32_to_nhwc_bf16(x.data_ptr(), n, c, h, w, 8, self.x_nhwc.data_ptr(),
                                                           _lib.stream_ptr(self.device)), "ryolo_nchw_f32_to_nhwc_bf16")
 
-    def _launch_all(self, x):
-        self._launch_input(x)
+    def _launch_layers(self):
         for op in self.ops:
             op()
+
+    def _launch_all(self, x):
+        self._launch_input(x)
+        self._launch_layers()
 
     def detect(self, x, conf_thres=0.5, nms_thres=0.5, capacity=1 << 18):
         """forward + post-processing for inference: the yolo layers run the fused decode + confidence filter +
@@ -342,9 +356,7 @@ class HipEngine(object):
         through ONE segmented rotated-NMS launch.  Returns what non_max_suppression(model(x)[0], conf_thres, nms_thres)
         returns: list[bs] of [k, 8] rows (x, y, w, h, a, score, class_conf, class) by descending score, or None."""
         from ..utils.nms.nms import nms_from_candidates
-        if tuple(x.shape) != (self.bs, x.shape[1], self.H, self.W) or x.shape[1] > 8:
-            raise RuntimeError("engine was planned for input %s" % ((self.bs, x.shape[1], self.H, self.W),))
-        x = x.float().contiguous()
+        x = self._as_input(x)
         L = _lib.lib()
         dev = self.device
         skip = set(d[0] for d in self.decodes)
@@ -380,14 +392,21 @@ class HipEngine(object):
                                        nc=self.no - 6)
 
     def __call__(self, x):
-        if tuple(x.shape) != (self.bs, x.shape[1], self.H, self.W) or x.shape[1] > 8:
-            raise RuntimeError("engine was planned for input %s" % ((self.bs, x.shape[1], self.H, self.W),))
-        if x.dtype != torch.float32:
-            x = x.float()
-        x = x.contiguous()
+        x = self._as_input(x)
         with torch.cuda.device(self.device):
             if not self.use_graph:
                 self._launch_all(x)
+            elif isinstance(x, NHWC8Batch):
+                # the batch goes into the input buffer in front of a graph of the layers alone (as in TrainEngine.forward); the graph of
+                # the fp32 path below owns a static fp32 input and the converter, and stays as it is
+                self._launch_input(x)
+                if self.graph_layers is None:
+                    self._launch_layers()                    # warm-up, as below
+                    torch.cuda.synchronize(self.device)
+                    self.graph_layers = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(self.graph_layers, capture_error_mode="thread_local"):
+                        self._launch_layers()
+                self.graph_layers.replay()
             else:
                 if self.graph is None:
                     self.static_x = x.clone()

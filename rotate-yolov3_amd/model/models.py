@@ -21,6 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..utils.parse_config import parse_model_cfg, parse_model_cfg_text, yolo_mask
+from .nhwc_batch import NHWC8Batch
 
 ARC_BIAS = {  # obj, cls bias targets per arc (models.py:133-146)
     'defaultpw': [-4, -3.6], 'Fdefaultpw': [-4, -3.6], 'default': [-5.5, -4.0], 'uBCE': [0, -8.5],
@@ -436,6 +437,8 @@ class Darknet(nn.Module):
         overwrites); training returns the head tensors p of the TrainEngine, which ARE engine buffers (1 GB at bs 64: not
         copied) -- consume them (compute_loss + backward) before the next forward."""
         if self.backend == 'torch' or not x.is_cuda:
+            if isinstance(x, NHWC8Batch):      # the ATen chain wants fp32 NCHW: ryolo_nhwc_bf16_to_nchw_f32
+                x = x.float()
             return self._torch_forward(x)
         if self.training:
             # hand-written HIP forward + backward (conv/BN/PReLU/shortcut/route/upsample); the returned head tensors

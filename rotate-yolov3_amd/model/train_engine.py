@@ -32,6 +32,7 @@ from . import hip_ops as ops
 from . import hip_train_ops as tr
 from . import plan
 from .engine import HipEngine
+from .nhwc_batch import NHWC8Batch
 
 
 class _Fn(torch.autograd.Function):
@@ -388,13 +389,18 @@ class TrainEngine(object):
 
     def forward(self, x):
         dev = self.device
-        x = x.float().contiguous()
+        nhwc = isinstance(x, NHWC8Batch)
+        if not nhwc:
+            x = x.float().contiguous()
         with torch.cuda.device(dev), torch.no_grad():
             # the input converter runs OUTSIDE the graph, reading the caller's tensor where it lies: the graph starts at the
             # engine's own NHWC buffer, so no 283-MB staging copy of the batch into a graph-owned tensor
-            n, c, h, w = x.shape
-            _lib.check(_lib.lib().ryolo_nchw_f32_to_nhwc_bf16(x.data_ptr(), n, c, h, w, 8, self.x_nhwc.data_ptr(), _lib.stream_ptr(dev)),
-                       "ryolo_nchw_f32_to_nhwc_bf16")
+            if nhwc:        # already the input layout (model/nhwc_batch.py): a device-to-device copy, or nothing when it IS the buffer
+                x.copy_into(self.x_nhwc)
+            else:
+                n, c, h, w = x.shape
+                _lib.check(_lib.lib().ryolo_nchw_f32_to_nhwc_bf16(x.data_ptr(), n, c, h, w, 8, self.x_nhwc.data_ptr(), _lib.stream_ptr(dev)),
+                           "ryolo_nchw_f32_to_nhwc_bf16")
             if not self.use_graph or self.steps < 2 or self.force_eager:       # two eager steps: lazy allocations, one-time attribute calls
                 self._forward_launch()
             else:

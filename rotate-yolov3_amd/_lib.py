@@ -1,10 +1,16 @@
 """ctypes binding of include/ryolo.h (libryolo_hip.so).
 
+The header is the only place a signature is written: importing this module parses it (no library needed) into `_sigs`,
+entry point -> (restype, argtypes) for every prototype, and into the ctypes.Structure classes of its `typedef struct`s
+(ConvDesc, PackJob, WgradReduceJob, SgdJob); lib() applies the whole table when it loads the library.  A type the parser
+has no mapping for fails the import -- nothing is guessed, nothing is left to ctypes' default of passing a C int.
+
 The library is built in-tree by __graft_entry__.build() (hipcc --offload-arch=gfx950).  There is NO fallback:
 if the shared object is missing, or a call returns an error code, a RuntimeError is raised.
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RYOLO_HIP_LIB: another build of the same sources (the ablation build of tools/mp_ablate.py); never a different implementation
@@ -14,60 +20,75 @@ _lib = None
 
 ACT_LINEAR, ACT_LEAKY, ACT_MISH = 0, 1, 2
 
-
-class ConvDesc(C.Structure):
-    """ryolo_conv_desc of include/ryolo.h"""
-    _fields_ = [("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int),
-                ("ksize", C.c_int), ("stride", C.c_int), ("pad", C.c_int),
-                ("in_cstride", C.c_int), ("out_cstride", C.c_int), ("res_cstride", C.c_int),
-                ("act", C.c_int), ("slope", C.c_float), ("upsample", C.c_int), ("tile", C.c_int)]
+_SCALARS = {"int": C.c_int, "float": C.c_float, "long long": C.c_longlong, "size_t": C.c_size_t}
+# what a pointer may point at; every pointer is passed as an address (c_void_p) but for the two exceptions in _ctype
+_POINTEES = {"void", "char", "float", "double", "int", "unsigned", "unsigned char", "long long", "int32_t", "int64_t", "uint8_t", "uint64_t"}
 
 
-_vp = C.c_void_p
-_dp = C.POINTER(ConvDesc)
-_sigs = {
-    "ryolo_strerror": (C.c_char_p, [C.c_int]),
-    "ryolo_abi_version": (C.c_int, []),
-    "ryolo_build_id": (C.c_char_p, []),
-    "ryolo_set_tuning": (C.c_int, [C.c_char_p, C.c_char_p]),
-    "ryolo_rnms_workspace_bytes": (C.c_size_t, [C.c_int]),
-    "ryolo_rnms": (C.c_int, [_vp, C.c_int, C.c_int, C.c_float, _vp, _vp, _vp, C.c_size_t, _vp]),
-    "ryolo_rnms_segmented_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "ryolo_rnms_segmented": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_float, _vp, _vp, C.c_size_t, _vp]),
-    "ryolo_riou_pairs": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
-    "ryolo_riou_matrix": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
-    "ryolo_rnms_count_pairs": (None, [_vp]),
-    "ryolo_skew_iou_pairs": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
-    "ryolo_skew_iou_matrix": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
-    "ryolo_eval_match_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "ryolo_eval_match": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp, _vp, C.c_size_t, _vp]),
-    # the dry-run queries of the layer planner (model/plan.py)
-    "ryolo_conv_pair_supported": (C.c_int, [_dp, _dp, C.c_int]),
-    "ryolo_conv_head_decode_supported": (C.c_int, [_dp, C.c_int, C.c_int]),
-    "ryolo_conv0_recompute_supported": (C.c_int, [_dp]),
-    "ryolo_conv2d_dgrad_bnreduce_rows": (C.c_int, [_dp]),
-    # gradients of the dilated shared 3x3 conv (csrc/conv_dil.hip, csrc/wgrad_dil.hip); the *_supported / workspace queries make no device call
-    "ryolo_conv2d_dilated_dgrad_supported": (C.c_int, [_dp, C.c_int, C.c_int]),
-    "ryolo_conv2d_dilated_dgrad": (C.c_int, [_dp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
-    "ryolo_conv2d_dilated_wgrad_supported": (C.c_int, [_dp, C.c_int, C.c_int]),
-    "ryolo_conv2d_dilated_wgrad_workspace_bytes": (C.c_size_t, [_dp, C.c_int, C.c_int]),
-    "ryolo_conv2d_dilated_wgrad": (C.c_int, [_dp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp]),
-    # squeeze-and-excitation (csrc/se.hip)
-    "ryolo_se_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "ryolo_se_nhwc": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp]),
-    # its backward (csrc/se_bwd.hip)
-    "ryolo_se_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "ryolo_se_bwd_nhwc": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int,
-                                    C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp]),
-}
+def _ctype(decl, named, structs, where):
+    """ctypes type of one C declarator of the header (`const float *const *ng`, `long long n`, `void`; named: it ends in an identifier)"""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    stars = words.count("*")
+    base = " ".join(w for w in (words[:-1] if named else words) if w != "*")
+    if not stars:
+        if base in _SCALARS:
+            return _SCALARS[base]
+    elif base == "char" and stars == 1:
+        return C.c_char_p
+    elif base in structs:      # the descriptor is always a host struct, passed with byref; the job structs are device arrays too
+        return C.POINTER(structs[base]) if base == "ryolo_conv_desc" and stars == 1 else C.c_void_p
+    elif base in _POINTEES:
+        return C.c_void_p
+    raise RuntimeError("include/ryolo.h: %s: no ctypes mapping for `%s`" % (where, " ".join(decl.split())))
 
 
-def declare(name, restype, argtypes):
-    """Other modules (conv, decode) register their entry points here so all signatures live in one table."""
-    _sigs[name] = (restype, argtypes)
-    if _lib is not None:
-        fn = getattr(getattr(_lib, "_real", _lib), name)
-        fn.restype, fn.argtypes = restype, argtypes
+def _parse_header(text):
+    """-> ({typedef name: ctypes.Structure class}, {entry point: (restype, argtypes)}) of the text of include/ryolo.h.  Handles the
+    forms that header uses and raises on anything else: block comments, # lines, extern "C", `typedef struct` bodies of scalar, array and
+    pointer fields, and prototypes over the closed type map above."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    structs, sigs = {}, {}
+
+    def struct(m):
+        body, name = m.group(1), m.group(2)
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            where = "struct %s, field `%s`" % (name, decl)
+            if "*" in decl:
+                fields.append((decl.split("*")[-1].strip(), _ctype(decl, True, structs, where)))
+                continue
+            first = decl.split(",")[0].split()
+            ctype = _ctype(" ".join(first), True, structs, where)
+            for item in [first[-1]] + decl.split(",")[1:]:
+                m2 = re.fullmatch(r"\s*(\w+)\s*(?:\[(\d+)\])?\s*", item)
+                if not m2:
+                    raise RuntimeError("include/ryolo.h: %s: not understood" % where)
+                fields.append((m2.group(1), ctype * int(m2.group(2)) if m2.group(2) else ctype))
+        cls = "".join(w.title() for w in name.split("_")[1:])      # ryolo_conv_desc -> ConvDesc
+        structs[name] = type(cls, (C.Structure,), {"_fields_": fields, "__doc__": "%s of include/ryolo.h" % name})
+        return ""
+
+    def proto(m):
+        ret, name, params = m.group(1), m.group(2), m.group(3).strip()
+        where = "prototype %s" % name
+        restype = None if ret.split() == ["void"] else _ctype(ret, False, structs, where)
+        argtypes = [] if params == "void" else [_ctype(p, True, structs, where) for p in params.split(",")]
+        sigs[name] = (restype, argtypes)
+        return ""
+
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\{([^}]*)\}\s*(\w+)\s*;", struct, text)
+    text = re.sub(r"([\w\s*]+?)\b(\w+)\s*\(([^()]*)\)\s*;", proto, text)
+    rest = text.replace('extern "C" {', "", 1).replace("}", "", 1).strip()
+    if rest:
+        raise RuntimeError("include/ryolo.h: not understood: `%s`" % " ".join(rest.split())[:120])
+    return structs, sigs
+
+
+with open(os.path.join(_HERE, os.pardir, "include", "ryolo.h")) as _fh:
+    _structs, _sigs = _parse_header(_fh.read())      # _sigs: entry point -> (restype, argtypes), every prototype of the header
+ConvDesc, PackJob = _structs["ryolo_conv_desc"], _structs["ryolo_pack_job"]
+WgradReduceJob, SgdJob = _structs["ryolo_wgrad_reduce_job"], _structs["ryolo_sgd_job"]
 
 
 def lib():
@@ -82,10 +103,15 @@ def lib():
         # process ends up with two, streams and memory from one, kernels registered with the other: every launch then fails
         # (seen as `build(); smoke()` in one process: "HIP launch failed")
         import torch  # noqa: F401
-        _lib = C.CDLL(LIB_PATH)
+        loaded = C.CDLL(LIB_PATH)
         for name, (restype, argtypes) in _sigs.items():
-            fn = getattr(_lib, name)
+            try:
+                fn = getattr(loaded, name)
+            except AttributeError:
+                raise RuntimeError("rotate-yolov3_amd: include/ryolo.h declares %s but %s does not export it -- rebuild the "
+                                   "library (__graft_entry__.build())" % (name, LIB_PATH))
             fn.restype, fn.argtypes = restype, argtypes
+        _lib = loaded
     return _lib
 
 

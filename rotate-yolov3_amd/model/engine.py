@@ -33,19 +33,6 @@ from . import plan
 from .nhwc_batch import NHWC8Batch
 from .plan import _abs  # noqa: F401  (the cfg's layer-index convention, for callers that walk module_defs themselves)
 
-_vp = C.c_void_p
-_lib.declare("ryolo_yolo_decode", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_float,
-                                            C.c_float, C.c_int, _vp, C.c_longlong, C.c_longlong, _vp, _vp])
-_lib.declare("ryolo_yolo_decode_filter", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_float,
-                                                   C.c_float, C.c_int, C.c_float, C.c_float, C.c_longlong, C.c_longlong, _vp,
-                                                   _vp, _vp, C.c_int, _vp])
-_lib.declare("ryolo_conv_head_decode", C.c_int, [C.POINTER(ops.ConvDesc), _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_float, C.c_float,
-                                                 C.c_int, _vp, C.c_longlong, C.c_longlong, _vp, _vp])
-_lib.declare("ryolo_add_nhwc", C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_longlong, C.c_int, _vp])
-_lib.declare("ryolo_upsample_nhwc", C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp])
-_lib.declare("ryolo_maxpool_nhwc", C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                             C.c_int, _vp])
-
 
 class HipEngine(object):
     def __init__(self, model, x_shape, device, use_graph=False, want_p=True):

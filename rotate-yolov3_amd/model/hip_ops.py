@@ -11,19 +11,6 @@ import torch
 from .. import _lib
 from .._lib import ACT_LEAKY, ACT_LINEAR, ACT_MISH, ConvDesc  # noqa: F401  (part of this module's interface)
 
-_vp = C.c_void_p
-_lib.declare("ryolo_conv_packed_weight_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int])
-_lib.declare("ryolo_conv_pack_weights", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp])
-_lib.declare("ryolo_conv2d_bn_act", C.c_int, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp])
-_lib.declare("ryolo_conv2d_bn_act_pair", C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp])
-_lib.declare("ryolo_conv2d_dilated_supported", C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int])
-_lib.declare("ryolo_conv2d_dilated", C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
-_lib.declare("ryolo_conv_kernel_choice", C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int])
-_lib.declare("ryolo_conv_dgrad_kernel_choice", C.c_int, [C.POINTER(ConvDesc), C.c_int])
-_lib.declare("ryolo_conv_wgrad_kernel_choice", C.c_int, [C.POINTER(ConvDesc)])
-_lib.declare("ryolo_nchw_f32_to_nhwc_bf16", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp])
-_lib.declare("ryolo_nhwc_bf16_to_nchw_f32", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp])
-
 
 def cpad(c, m=128):
     return (c + m - 1) // m * m

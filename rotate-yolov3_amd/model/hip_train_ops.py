@@ -6,55 +6,10 @@ import ctypes as C
 import torch
 
 from .. import _lib
+from .._lib import PackJob, WgradReduceJob
 from . import hip_ops
 from .hip_ops import ConvDesc, _check_nhwc, cpad, pack_weights
 
-_vp = C.c_void_p
-_P = C.POINTER(ConvDesc)
-_lib.declare("ryolo_conv_stat_rows", C.c_int, [_P])
-_lib.declare("ryolo_conv2d_bn_act_stats", C.c_int, [_P, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
-_lib.declare("ryolo_bn_finalize", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_float, C.c_float, _vp, _vp, _vp,
-                                            _vp, _vp, _vp, _vp, _vp, _vp])
-_lib.declare("ryolo_bn_act_fwd", C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_longlong,
-                                           C.c_int, _vp])
-_lib.declare("ryolo_bn_act_bwd_workspace_bytes", C.c_size_t, [C.c_longlong, C.c_int])
-_lib.declare("ryolo_bn_act_bwd", C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int,
-                                           C.c_longlong, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp])
-_lib.declare("ryolo_conv_packed_dgrad_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int])
-_lib.declare("ryolo_conv_pack_weights_dgrad", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp])
-_lib.declare("ryolo_conv_dgrad_tap_table", C.c_int, [C.c_int, C.c_int, _vp])
-_lib.declare("ryolo_conv2d_dgrad", C.c_int, [_P, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp])
-_lib.declare("ryolo_conv2d_dgrad_bnreduce", C.c_int, [_P, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp,
-                                                      _vp, _vp])
-_lib.declare("ryolo_bn_act_bwd_reduced", C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int,
-                                                   C.c_longlong, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_size_t, _vp])
-_lib.declare("ryolo_conv_wgrad_workspace_bytes", C.c_size_t, [_P])
-_lib.declare("ryolo_conv2d_wgrad", C.c_int, [_P, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp])
-_lib.declare("ryolo_conv2d_wgrad_partials", C.c_int, [_P, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp])
-_lib.declare("ryolo_conv2d_wgrad_reduce", C.c_int, [_P, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_size_t, _vp])
-_lib.declare("ryolo_conv_head_decode_store", C.c_int, [_P, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp])
-_lib.declare("ryolo_upsample2x_bwd", C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp])
-_lib.declare("ryolo_pgrad_to_nhwc", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp])
-
-
-_lib.declare("ryolo_yolo_loss_bitmap_bytes", C.c_size_t, [C.c_longlong])
-_lib.declare("ryolo_yolo_loss", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp,
-                                          _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                          C.c_float, C.c_int, _vp, _vp, _vp, _vp])
-_lib.declare("ryolo_yolo_loss_nhwc", C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp,
-                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, C.c_float, C.c_float, C.c_float,
-                                               C.c_float, C.c_float, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp])
-_lib.declare("ryolo_scale_bf16_if", C.c_int, [_vp, _vp, C.c_int, C.c_longlong, C.c_int, _vp])
-_lib.declare("ryolo_yolo_loss_bitmap_bytes_arc", C.c_size_t, [C.c_longlong, C.c_int, C.c_int])
-_lib.declare("ryolo_yolo_loss_arc", C.c_int, [_vp] + [C.c_int] * 6 + [_vp, C.c_int] + [_vp] * 9 + [C.c_float] * 6 +
-             [C.c_int, C.c_int, C.c_float] + [_vp] * 4)
-_lib.declare("ryolo_yolo_loss_nhwc_arc", C.c_int, [_vp, C.c_int, _vp] + [C.c_int] * 6 + [_vp, C.c_int] + [_vp] * 9 + [C.c_float] * 6 +
-             [C.c_int, C.c_int, C.c_float] + [_vp, _vp, _vp, C.c_int, _vp, _vp])
-_lib.declare("ryolo_yolo_loss_bias_rows", C.c_int, [C.c_int] * 6)
-_lib.declare("ryolo_yolo_loss_nhwc_bias", C.c_int, [_vp, C.c_int, _vp] + [C.c_int] * 6 + [_vp, C.c_int] + [_vp] * 9 + [C.c_float] * 6 +
-             [C.c_int, C.c_int, C.c_float] + [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp])
-_lib.declare("ryolo_head_bias_workspace_bytes", C.c_size_t, [C.c_longlong, C.c_int])
-_lib.declare("ryolo_head_bias_finalize", C.c_int, [_vp, C.c_longlong, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp])
 ARC_FOCAL, ARC_UBCE, ARC_UCE = 1, 2, 4
 
 
@@ -69,28 +24,6 @@ def arc_flags(arc):
     if 'CE' in arc:
         return f | ARC_UCE
     raise ValueError("unknown arc %r" % (arc,))
-_lib.declare("ryolo_riou_loss_pairs", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp])
-
-
-class PackJob(C.Structure):
-    """ryolo_pack_job (include/ryolo.h)."""
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("kind", C.c_int), ("Cout", C.c_int), ("Cin", C.c_int),
-                ("KS", C.c_int), ("Cin_pad", C.c_int), ("ntaps", C.c_int), ("Kpad", C.c_int), ("rows", C.c_int),
-                ("khs", C.c_int * 9), ("kws", C.c_int * 9), ("block_begin", C.c_int), ("block_end", C.c_int)]
-
-
-_lib.declare("ryolo_conv_pack_job_fill", C.c_int, [C.POINTER(PackJob), _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp])
-_lib.declare("ryolo_conv_pack_batch", C.c_int, [_vp, C.c_int, C.c_int, _vp])
-
-
-class WgradReduceJob(C.Structure):
-    _fields_ = [("part", C.c_void_p), ("g", C.c_void_p), ("S", C.c_int), ("Cout", C.c_int), ("Cin_real", C.c_int), ("Cin_k", C.c_int),
-                ("ks", C.c_int), ("Kpad", C.c_int), ("Cout_pad", C.c_int), ("accumulate", C.c_int), ("kind", C.c_int),
-                ("block_begin", C.c_int), ("block_end", C.c_int), ("wide", C.c_int)]
-
-
-_lib.declare("ryolo_conv_wgrad_reduce_job_fill", C.c_int, [C.POINTER(WgradReduceJob), _P, C.c_int, _vp, _vp, C.c_int])
-_lib.declare("ryolo_conv_wgrad_reduce_batch", C.c_int, [_vp, C.c_int, C.c_int, _vp])
 
 
 class WgradReduceBatch(object):
@@ -207,12 +140,6 @@ def conv_fwd_stats(d, x, packed_w, ones, shift, z, part=None, clear=True):
     return part
 
 
-_lib.declare("ryolo_conv0_bn_act_fwd", C.c_int, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp])
-_lib.declare("ryolo_conv0_bn_bwd_workspace_bytes", C.c_size_t, [])
-_lib.declare("ryolo_conv0_bn_bwd", C.c_int, [C.POINTER(ConvDesc), _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int,
-                                             _vp, _vp, _vp, _vp, C.c_size_t, C.c_int, _vp])
-
-
 def conv0_recompute_supported(d):
     """Layer 0 (3x3 / stride 1 / pad 1, 8 padded input channels -> 32): train without storing the conv output (include/ryolo.h)."""
     return bool(_lib.lib().ryolo_conv0_recompute_supported(C.byref(d)))
@@ -241,11 +168,6 @@ def conv0_bn_bwd(d, x, packed_w, dy, stats, act, slope, dz, dgamma, dbeta, dslop
                                              dgamma.data_ptr(), dbeta.data_ptr(), dslope.data_ptr() if dslope is not None else None,
                                              ws.data_ptr(), ws.numel(), 1 if ws_is_zero else 0, _s(x.device)), "ryolo_conv0_bn_bwd")
     return dz
-
-
-_lib.declare("ryolo_conv0_bn_bwd_wgrad_workspace_bytes", C.c_size_t, [])
-_lib.declare("ryolo_conv0_bn_bwd_wgrad", C.c_int, [C.POINTER(ConvDesc), _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp,
-                                                  _vp, C.c_int, C.c_int, _vp, C.c_size_t, _vp])
 
 
 def conv0_bn_bwd_wgrad_ws(device):
@@ -707,10 +629,6 @@ class RotatedIoU(torch.autograd.Function):
     def backward(ctx, g):
         (grad,) = ctx.saved_tensors
         return grad * g.unsqueeze(1), None
-
-
-_lib.declare("ryolo_build_targets", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_float, C.c_float, C.c_float, _vp, _vp,
-                                              _vp, _vp, _vp])
 
 
 class BuildTargets(object):

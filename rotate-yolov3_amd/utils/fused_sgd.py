@@ -3,19 +3,10 @@ with the whole step as ONE HIP launch (csrc/optim.hip) instead of ATen's ~30 for
 tensors of Darknet-53.  Same arithmetic in the same order; same `param_groups` / `state[p]['momentum_buffer']` layout, so
 `state_dict()` is interchangeable with torch.optim.SGD's.  Parameters that are not fp32 CUDA tensors, dampening,
 maximize and differentiable are not supported (construct torch.optim.SGD for those)."""
-import ctypes as C
-
 import torch
 
 from .. import _lib
-
-
-class _Job(C.Structure):
-    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("buf", C.c_void_p), ("n", C.c_longlong), ("group", C.c_int),
-                ("first", C.c_int), ("block_begin", C.c_int), ("block_end", C.c_int)]
-
-
-_lib.declare("ryolo_sgd_step", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p])
+from .._lib import SgdJob as _Job
 
 
 class FusedSGD(torch.optim.Optimizer):

@@ -22,7 +22,7 @@ import rotate_yolov3_amd  # noqa: F401  (installs the package under its importab
 from rotate_yolov3_amd import _lib
 from rotate_yolov3_amd.cfg import make_cfg
 from rotate_yolov3_amd.model import hip_ops as ops
-from rotate_yolov3_amd.model import hip_train_ops as tr  # noqa: F401  (declares the weight-gradient queries)
+from rotate_yolov3_amd.model import hip_train_ops as tr
 from rotate_yolov3_amd.model import plan
 from rotate_yolov3_amd.utils.parse_config import parse_model_cfg_text, yolo_mask
 

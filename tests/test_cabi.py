@@ -12,31 +12,31 @@ def _declared():
     return sorted(set(re.findall(r"\b(ryolo_[a-z0-9_]+)\s*\(", src)))
 
 
-def test_library_exports_every_declared_symbol():
+def _binding():
+    """the package's binding of the built library: every signature from include/ryolo.h (rotate-yolov3_amd/_lib.py)"""
     import __graft_entry__ as g
     if not os.path.exists(g.LIB):
         g.build()
-    lib = ctypes.CDLL(g.LIB)
+    import rotate_yolov3_amd  # noqa: F401
+    from rotate_yolov3_amd import _lib
+    return _lib.lib()
+
+
+def test_library_exports_every_declared_symbol():
+    lib = _binding()
     names = _declared()
     assert "ryolo_rnms" in names and "ryolo_conv2d_bn_act" in names
     for n in names:
         assert hasattr(lib, n), "include/ryolo.h declares %s but libryolo_hip.so does not export it" % n
-    lib.ryolo_abi_version.restype = ctypes.c_int
     assert lib.ryolo_abi_version() >= 1
-    lib.ryolo_strerror.restype = ctypes.c_char_p
     assert lib.ryolo_strerror(-1) == b"invalid argument"
 
 
 def test_argument_validation_without_gpu():
     # pure host-side checks: they return before anything is enqueued
-    import __graft_entry__ as g
-    lib = ctypes.CDLL(g.LIB)
-    lib.ryolo_rnms.restype = ctypes.c_int
-    vp = ctypes.c_void_p
-    lib.ryolo_rnms.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, vp, vp, vp, ctypes.c_size_t, vp]
+    lib = _binding()
     assert lib.ryolo_rnms(None, -1, 6, 0.5, None, None, None, 0, None) == -1
     assert lib.ryolo_rnms(None, 5, 6, 0.5, None, ctypes.c_void_p(16), None, 0, None) == -1
-    lib.ryolo_conv_packed_weight_bytes.restype = ctypes.c_size_t
     assert lib.ryolo_conv_packed_weight_bytes(504, 1024, 1) == (512 * 1024 + 128) * 2
     assert lib.ryolo_conv_packed_weight_bytes(32, 8, 3) == (128 * 128 + 128) * 2
     assert lib.ryolo_conv_packed_weight_bytes(32, 8, 5) == 0
@@ -46,11 +46,7 @@ def test_tuning_switches_are_a_closed_set_and_the_library_reads_no_environment_o
     """round 6: six documented switches, set in-process through ryolo_set_tuning; an unknown name is an
     error; and the product sources call getenv in exactly one place (the once-only initialisation of those six) -- every other
     environment switch of rounds 3-5 lives behind -DRYOLO_MP_ABLATION."""
-    import __graft_entry__ as g
-    lib = ctypes.CDLL(g.LIB)
-    lib.ryolo_set_tuning.restype = ctypes.c_int
-    lib.ryolo_set_tuning.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
-    import rotate_yolov3_amd  # noqa: F401
+    lib = _binding()
     from rotate_yolov3_amd import _lib
     assert len(_lib.TUNING_SWITCHES) == 6
     for name in _lib.TUNING_SWITCHES:
@@ -126,16 +122,12 @@ def test_r_nms_rejects_cpu_tensors_like_the_reference():
 def test_host_side_planning_helpers():
     """Host-only entry points (no kernel launch): dgrad tap tables, packed sizes, pack-job layout, workspace sizes."""
     import ctypes as C
-    import __graft_entry__ as g
-    lib = C.CDLL(g.LIB)
+    lib = _binding()
     # stride-1 dgrad of a 3x3 conv visits all 9 taps; stride 2 splits them over the 4 output-parity classes as 1 + 2 + 2 + 4
     tab = (C.c_int * 72)()
-    lib.ryolo_conv_dgrad_tap_table.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
     assert lib.ryolo_conv_dgrad_tap_table(3, 1, tab) == 0
     taps = sorted((tab[t], tab[9 + t]) for t in range(9))
     assert taps == [(a, b) for a in range(3) for b in range(3)]
-    lib.ryolo_conv_packed_dgrad_bytes.restype = C.c_size_t
-    lib.ryolo_conv_packed_dgrad_bytes.argtypes = [C.c_int] * 4
     cout, cin = 128, 96      # (C_in 32 / 64 stride-2 convs carry two more, x-fused, images: below)
     s1 = lib.ryolo_conv_packed_dgrad_bytes(cout, cin, 3, 1)
     s2 = lib.ryolo_conv_packed_dgrad_bytes(cout, cin, 3, 2)
@@ -144,13 +136,8 @@ def test_host_side_planning_helpers():
     assert s1 == (rows * kp(9) + 128) * 2
     assert s2 == sum((rows * kp(nt) + 128) * 2 for nt in (1, 2, 2, 4))
 
-    class Job(C.Structure):
-        _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("kind", C.c_int), ("Cout", C.c_int), ("Cin", C.c_int),
-                    ("KS", C.c_int), ("Cin_pad", C.c_int), ("ntaps", C.c_int), ("Kpad", C.c_int), ("rows", C.c_int),
-                    ("khs", C.c_int * 9), ("kws", C.c_int * 9), ("block_begin", C.c_int), ("block_end", C.c_int)]
-    lib.ryolo_conv_pack_job_fill.argtypes = [C.POINTER(Job), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                             C.c_void_p]
-    jobs = (Job * 8)()
+    from rotate_yolov3_amd.model import hip_train_ops as tr
+    jobs = (tr.PackJob * 8)()
     fake = C.c_void_p(4096)
     assert lib.ryolo_conv_pack_job_fill(jobs, fake, cout, cin, 3, 1, cin, fake, None) == 1
     assert lib.ryolo_conv_pack_job_fill(jobs, fake, cout, cin, 3, 1, cin, fake, fake) == 2
@@ -167,10 +154,8 @@ def test_host_side_planning_helpers():
     assert lib.ryolo_conv_packed_dgrad_bytes(64, 32, 3, 2) == sum((128 * kp64(nt) + 128) * 2 for nt in (1, 2, 2, 4, 2, 4))
     # split-K reduce jobs (round 5: the reduces of a backward segment as one launch): the job describes the layer's partial tiles
     # exactly as the tile kernels lay them out, so S x Kpad x Cout_pad floats must fit in the layer's own workspace
-    import rotate_yolov3_amd  # noqa: F401
     from rotate_yolov3_amd import _lib
     from rotate_yolov3_amd.model import hip_ops as ops
-    from rotate_yolov3_amd.model import hip_train_ops as tr
     assert C.sizeof(tr.WgradReduceJob) == 64
     for (n, h, ci, co, k, st) in [(64, 76, 128, 256, 3, 1), (64, 19, 1024, 512, 1, 1), (64, 19, 512, 1024, 3, 1), (64, 304, 32, 64, 3, 2),
                                   (64, 608, 8, 32, 3, 1), (2, 19, 1024, 512, 1, 1)]:
@@ -185,11 +170,7 @@ def test_host_side_planning_helpers():
         assert _lib.lib().ryolo_conv_wgrad_reduce_job_fill(C.byref(j), C.byref(d), ci, None, 8192, 1) == 0
     assert _lib.lib().ryolo_conv_wgrad_reduce_batch(None, 1, 1, None) != 0
     # workspace queries
-    lib.ryolo_rnms_workspace_bytes.restype = C.c_size_t
-    lib.ryolo_rnms_segmented_workspace_bytes.restype = C.c_size_t
     assert 0 < lib.ryolo_rnms_workspace_bytes(1000) < lib.ryolo_rnms_workspace_bytes(50000)
     assert lib.ryolo_rnms_segmented_workspace_bytes(64000, 32, 2000) < lib.ryolo_rnms_workspace_bytes(64000)
     assert lib.ryolo_rnms_segmented_workspace_bytes(0, 1, 1) == 0
-    lib.ryolo_yolo_loss_bitmap_bytes.restype = C.c_size_t
-    lib.ryolo_yolo_loss_bitmap_bytes.argtypes = [C.c_longlong]
     assert lib.ryolo_yolo_loss_bitmap_bytes(33) == 8 and lib.ryolo_yolo_loss_bitmap_bytes(0) == 0

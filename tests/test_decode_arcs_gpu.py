@@ -31,7 +31,6 @@ DEC_PIX, TILE_LIMIT = 32, 64 * 1024   # csrc/yolo.hip: pixels per tile, the tile
 
 def _lib():
     from rotate_yolov3_amd import _lib as L
-    from rotate_yolov3_amd.model import engine  # noqa: F401  (declares the entry points' signatures)
     return L
 
 

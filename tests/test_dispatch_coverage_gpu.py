@@ -33,7 +33,7 @@ GUARD = 4096
 @pytest.fixture(scope="module")
 def env(cuda_dev):
     from rotate_yolov3_amd import _lib
-    from rotate_yolov3_amd.model import engine, hip_ops, hip_train_ops  # noqa: F401  (engine declares ryolo_conv_head_decode, which the head cases launch)
+    from rotate_yolov3_amd.model import hip_ops, hip_train_ops
     torch.backends.cuda.matmul.allow_tf32 = False
     torch.backends.cudnn.allow_tf32 = False
     cus = torch.cuda.get_device_properties(cuda_dev).multi_processor_count

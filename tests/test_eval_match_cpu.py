@@ -17,7 +17,9 @@ def _lib():
     import __graft_entry__ as g
     if not os.path.exists(g.LIB):
         g.build()
-    return C.CDLL(g.LIB)
+    import rotate_yolov3_amd  # noqa: F401
+    from rotate_yolov3_amd import _lib as binding
+    return binding.lib()
 
 
 def test_header_declares_and_library_exports_the_matcher():
@@ -35,11 +37,7 @@ def test_header_declares_and_library_exports_the_matcher():
 def test_argument_validation_without_gpu():
     lib = _lib()
     vp = C.c_void_p
-    ws_bytes = lib.ryolo_eval_match_workspace_bytes
-    ws_bytes.restype, ws_bytes.argtypes = C.c_size_t, [C.c_int, C.c_int]
-    f = lib.ryolo_eval_match
-    f.restype = C.c_int
-    f.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, C.c_size_t, vp]
+    ws_bytes, f = lib.ryolo_eval_match_workspace_bytes, lib.ryolo_eval_match
     p = vp(4096)                        # never dereferenced: every call below returns from the host-side checks
     big = 1 << 20
 

@@ -20,7 +20,6 @@ BF = torch.bfloat16
 
 def _lib():
     from rotate_yolov3_amd import _lib as L
-    from rotate_yolov3_amd.model import engine, hip_ops  # noqa: F401  (declare the entry points' signatures)
     return L
 
 

@@ -43,7 +43,6 @@ CASE_B = (26000, 9002, 102)
 def L(cuda_dev):
     import rotate_yolov3_amd  # noqa: F401
     from rotate_yolov3_amd import _lib
-    from rotate_yolov3_amd.model import engine as _eng  # noqa: F401  (declares ryolo_yolo_decode_filter's signature)
     return _lib
 
 

@@ -13,7 +13,6 @@ import torch
 import rotate_yolov3_amd  # noqa: F401
 from rotate_yolov3_amd import _lib
 from rotate_yolov3_amd.cfg import make_cfg
-from rotate_yolov3_amd.model import engine  # noqa: F401  (declares ryolo_yolo_decode)
 from rotate_yolov3_amd.model import hip_ops as ops
 from rotate_yolov3_amd.model import hip_train_ops as tr
 from rotate_yolov3_amd.model.loss import compute_loss

@@ -21,7 +21,6 @@ sys.path.insert(0, ROOT)
 import rotate_yolov3_amd  # noqa: E402,F401
 from rotate_yolov3_amd import _lib  # noqa: E402
 from rotate_yolov3_amd.cfg import make_cfg  # noqa: E402
-from rotate_yolov3_amd.model import engine as _engine  # noqa: E402,F401  (declares ryolo_add_nhwc)
 from rotate_yolov3_amd.model import hip_ops as ops  # noqa: E402
 from rotate_yolov3_amd.model.engine import HipEngine  # noqa: E402
 from rotate_yolov3_amd.model.models import Darknet  # noqa: E402

@@ -267,6 +267,33 @@ int ryolo_conv2d_dilated_wgrad(const ryolo_conv_desc *forward_desc, int dil_h, i
 int ryolo_nchw_f32_to_nhwc_bf16(const float *x, int N, int C, int H, int W, int Cpad, void *y, void *stream);
 int ryolo_nhwc_bf16_to_nchw_f32(const void *x, int N, int C, int H, int W, int cstride, float *y, void *stream);
 
+/* Real-data input (csrc/augment.hip) -- replaces, on the device, what LoadImagesAndLabels.__getitem__ does to the pixels of one image
+ * (utils/datasets.py:431-451 letterbox, :470-484 + utils/augment.py the Transform chain, :498-500 the [0, 1] scaling): one launch turns
+ * N cached uint8 images into the engines' input, bf16 [N][H][W][8] with channels 3..7 zero -- bit for bit what
+ * ryolo_nchw_f32_to_nhwc_bf16 makes of the fp32 image when the map is the identity.
+ *   pixels      the cache: RGB uint8 HWC images of different sizes, back to back; image i starts at byte img_offset[i] and is
+ *               img_hw[i] = (h, w) pixels.  src_index[n] selects the cached image of batch slot n (one outside [0, n_cache) reads
+ *               nothing: the slot is all border).
+ *   params      [N][ryolo_aug_nparam() = 16] fp32 rows: m00 m01 m02 m10 m11 m12 | noise_sigma | gamma | gamma_max | blur_sigma |
+ *               sat_gain | val_gain | gray_alpha | three reserved zeros.  The matrix maps an OUTPUT pixel index (x, y) to source pixel
+ *               coordinates, sx = m00 x + m01 y + m02, sy = m10 x + m11 y + m12: letterbox resize and padding, the random affine and both
+ *               flips are folded into it by the host.  Neutral: 0, 1, any, 0, 1, 1, 0; a neutral stage is skipped, exactly.
+ *   seed        keys the noise: a counter-based hash of (seed, n, y, x), no state, the same call gives the same bits.
+ * Stages, fp32 on a 0..255 scale, never quantised in between (the full definition, with the hash written out in 32-bit operations, is
+ * the header comment of csrc/augment.hip; tests/augment_reference.py restates it in float64):
+ *   bilinear sample, taps outside the source = 128  ->  + noise_sigma * z (one z per pixel), clamp  ->  powf(v / gamma_max, gamma) *
+ *   gamma_max  ->  separable Gaussian blur over the output grid, taps |d| <= 4, BORDER_REFLECT_101, blur_sigma above
+ *   ryolo_aug_max_blur_sigma() = 1.5 taken as that  ->  saturation / value gains in the hue-free closed form  ->  blend towards
+ *   0.299 R + 0.587 G + 0.114 B by gray_alpha  ->  clamp, / 255.0f, round to nearest even bf16.
+ * One launch on `stream`: 256-thread workgroups own 32 x 32 output tiles; no workspace, no allocation, no atomics, one writer per
+ * element, capture-safe, bit-identical from run to run.  RYOLO_EINVAL before any HIP call: a null pointer (other than stream), N, H, W
+ * or n_cache < 1, N or the row-tile count above 65535, y not 16-byte aligned.  The two queries need no device. */
+int ryolo_aug_nparam(void);
+float ryolo_aug_max_blur_sigma(void);
+int ryolo_letterbox_augment(const uint8_t *pixels, const long long *img_offset, const int *img_hw /* [n_cache][2] */, int n_cache,
+                            const int *src_index /* [N] */, const float *params /* [N][16] */, long long seed, int N, int H, int W,
+                            void *y /* bf16 [N][H][W][8] */, void *stream);
+
 
 /* Decode + score filter + compaction (no `io` tensor): the rows of ryolo_yolo_decode's `io` that the first half of
  * non_max_suppression keeps (utils/nms/nms.py:33-48: class_conf/class = max over io[6:], score = io[5]*class_conf,

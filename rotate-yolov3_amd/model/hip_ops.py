@@ -227,6 +227,42 @@ def nchw_f32_to_nhwc_bf16(x, cpad_to=8):
     return y
 
 
+def letterbox_augment(cache, src_index, params, seed, H, W, out=None):
+    """One launch of csrc/augment.hip: batch slot n = the cached image src_index[n], sampled through the matrix of params[n] and put
+    through its photometric stages (include/ryolo.h: ryolo_letterbox_augment) -> NHWC8Batch of [N, H, W, 8].
+    cache: the device image cache (utils.datasets.DeviceImageCache: .pixels uint8, .img_offset int64 [n], .img_hw int32 [n, 2]);
+    src_index: int32 [N]; params: fp32 [N, 16]; both on the cache's device.  out: a bf16 [N, H, W, 8] tensor to write into."""
+    from .nhwc_batch import NHWC8Batch
+    L = _lib.lib()
+    pixels, offs, hw = cache.pixels, cache.img_offset, cache.img_hw
+    dev = pixels.device
+    if not (pixels.is_cuda and pixels.dtype == torch.uint8 and pixels.is_contiguous()):
+        raise RuntimeError("cache.pixels must be a contiguous uint8 GPU tensor")
+    n_cache = offs.numel()
+    if not (offs.dtype == torch.int64 and offs.is_contiguous() and offs.device == dev and hw.dtype == torch.int32 and hw.is_contiguous()
+            and hw.device == dev and tuple(hw.shape) == (n_cache, 2)):
+        raise RuntimeError("cache.img_offset / cache.img_hw must be int64 [n] / int32 [n, 2] tensors on the cache's device")
+    if not torch.is_tensor(src_index):
+        src_index = torch.tensor(list(src_index), dtype=torch.int32, device=dev)
+    if not torch.is_tensor(params):
+        params = torch.as_tensor(params, dtype=torch.float32).to(dev)
+    n = src_index.numel()
+    if not (src_index.dtype == torch.int32 and src_index.dim() == 1 and src_index.is_contiguous() and src_index.device == dev):
+        raise RuntimeError("src_index must be a contiguous int32 [N] tensor on the cache's device")
+    if not (params.dtype == torch.float32 and params.is_contiguous() and params.device == dev
+            and tuple(params.shape) == (n, L.ryolo_aug_nparam())):
+        raise RuntimeError("params must be a contiguous fp32 [N, %d] tensor on the cache's device" % L.ryolo_aug_nparam())
+    if out is None:
+        out = torch.empty((n, H, W, 8), dtype=torch.bfloat16, device=dev)
+    elif not (out.dtype == torch.bfloat16 and out.is_contiguous() and out.device == dev and tuple(out.shape) == (n, H, W, 8)):
+        raise RuntimeError("out must be a contiguous bf16 [N, H, W, 8] tensor on the cache's device")
+    with torch.cuda.device(dev):
+        _lib.check(L.ryolo_letterbox_augment(pixels.data_ptr(), offs.data_ptr(), hw.data_ptr(), n_cache, src_index.data_ptr(),
+                                             params.data_ptr(), int(seed), n, int(H), int(W), out.data_ptr(), _lib.stream_ptr(dev)),
+                   "ryolo_letterbox_augment")
+    return NHWC8Batch(out)
+
+
 def nhwc_bf16_to_nchw_f32(x):
     cs = _check_nhwc(x, "x")
     n, h, w, c = x.shape

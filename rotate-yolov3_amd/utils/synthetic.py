@@ -1,5 +1,5 @@
-"""Synthetic HRSC-shaped data: the benchmarks and entry points run without the
-reference's OpenCV/imgaug input pipeline (utils/datasets.py, utils/augment.py -- out of scope, CPU side)."""
+"""Synthetic HRSC-shaped data: the benchmarks, and the entry points without --real-data, run without
+images on disk (the real-data path: utils/datasets.py over csrc/augment.hip)."""
 import math
 
 import torch

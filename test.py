@@ -3,7 +3,8 @@
 forward (HIP engine) -> non_max_suppression -> greedy matching on rotated IoU -> ap_per_class.
 The reference matches predictions with a per-pair Python + shapely loop (test.py:134-151, utils/utils.py:290-320);
 here one `ryolo_eval_match` call per batch (three launches, one device -> host transfer), or with batched_match=False one
-`ryolo_skew_iou_matrix` launch and a host loop per image.  Data: synthetic loader (the OpenCV loader is out of scope)."""
+`ryolo_skew_iou_matrix` launch and a host loop per image.  Data: the synthetic loader, or with --real-data the `valid` image list of
+--data through the device loader (utils/datasets.py, csrc/augment.hip: letterbox only, no augmentation)."""
 import argparse
 import os
 import sys
@@ -48,7 +49,8 @@ def _batch_stats(stats, inf_out, targets, width, height, iou_thres, conf_thres, 
 
 
 def test(cfg, hyp, weights=None, batch_size=16, img_size=608, iou_thres=0.5, conf_thres=0.001, nms_thres=0.5, model=None,
-         n_images=32, device=None, nc=None, batched_match=True):
+         n_images=32, device=None, nc=None, batched_match=True, loader=None):
+    """loader: batches to evaluate (utils.datasets.LoadImagesAndLabels); None: n_images synthetic ones"""
     device = device or torch.device('cuda:0')
     if model is None:
         model = Darknet(cfg, hyp)
@@ -63,7 +65,7 @@ def test(cfg, hyp, weights=None, batch_size=16, img_size=608, iou_thres=0.5, con
     seen = 0
     stats = []
     with torch.no_grad():
-        for imgs, targets, _, _ in SyntheticLoader(n_images, batch_size, img_size, seed=1, device=device):
+        for imgs, targets, _, _ in (loader if loader is not None else SyntheticLoader(n_images, batch_size, img_size, seed=1, device=device)):
             _, _, height, width = imgs.shape
             inf_out, train_out = model(imgs)
             if batched_match:
@@ -107,7 +109,7 @@ if __name__ == '__main__':
     parser = argparse.ArgumentParser(prog='test.py')                     # the reference's flags (test.py:206-216), same defaults
     parser.add_argument('--hyp', type=str, default='cfg/ICDAR/hyp.py', help='hyper-parameter path')
     parser.add_argument('--cfg', type=str, default='cfg/ICDAR/yolov3_608_se.cfg', help='cfg file path')
-    parser.add_argument('--data', type=str, default='data/icdar_13+15.data', help='*.data file path (only `classes` is read: the image lists feed the out-of-scope OpenCV loader)')
+    parser.add_argument('--data', type=str, default='data/icdar_13+15.data', help='*.data file path (`classes`; with --real-data also `valid`, the image list)')
     parser.add_argument('--weights', type=str, default='weights/best.pt', help='path to weights file (.pt or darknet .weights)')
     parser.add_argument('--batch-size', type=int, default=1, help='size of each image batch')
     parser.add_argument('--img-size', type=int, default=608, help='inference size (pixels)')
@@ -115,7 +117,8 @@ if __name__ == '__main__':
     parser.add_argument('--conf-thres', type=float, default=0.001, help='object confidence threshold')
     parser.add_argument('--nms-thres', type=float, default=0.5, help='iou threshold for non-maximum suppression')
     parser.add_argument('--device', default='', help="device id (i.e. 0 or 0,1); the evaluation path has no CPU fallback")
-    parser.add_argument('--synthetic', type=int, default=32, help='synthetic images to evaluate (this build has no image loader)')
+    parser.add_argument('--synthetic', type=int, default=32, help='synthetic images to evaluate (without --real-data)')
+    parser.add_argument('--real-data', action='store_true', help='evaluate the `valid` image list of --data instead of synthetic images (needs Pillow)')
     ignored = add_ignored(parser, [('--save-json', dict(action='store_true', help='save a cocoapi-compatible JSON results file'))])
     opt = parser.parse_args()
     print(opt)
@@ -126,6 +129,10 @@ if __name__ == '__main__':
     weights = opt.weights if os.path.isfile(opt.weights) else ''
     if opt.weights and not weights:
         print('NOTE: weights file %r not found: evaluating the freshly initialised model' % opt.weights)
+    loader = None
+    if opt.real_data:
+        from rotate_yolov3_amd.utils.datasets import LoadImagesAndLabels
+        loader = LoadImagesAndLabels(parse_data_cfg(opt.data)['valid'], opt.img_size, opt.batch_size, augment=False, device=device)
     test(opt.cfg, hyp_parse(opt.hyp), weights, opt.batch_size, opt.img_size, opt.iou_thres, opt.conf_thres, opt.nms_thres,
          n_images=opt.synthetic, device=device,
-         nc=int(parse_data_cfg(opt.data)['classes']) if os.path.isfile(opt.data) else None)
+         nc=int(parse_data_cfg(opt.data)['classes']) if os.path.isfile(opt.data) else None, loader=loader)

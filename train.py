@@ -7,8 +7,9 @@ Kept: cfg / data / hyp files, Darknet(cfg, hyp, arc), the two optimizer paramete
 accumulation, the non-finite-loss abort, results.txt rows and the checkpoint dict (train.py:323-363).
 Changed: data parallelism is ONE PROCESS PER GPU (launch with `python -m torch.distributed.run --nproc-per-node N
 train.py ...`) with bucketed RCCL all-reduce overlapped with backward (rotate-yolov3_amd/dist.py) instead of the
-reference's broken single-process DDP; the input pipeline is synthetic (`--synthetic N` images per epoch) because the
-OpenCV/imgaug loader is out of scope.  On a GPU the training-mode forward AND backward run the hand-written HIP
+reference's broken single-process DDP; the input pipeline is synthetic (`--synthetic N` images per epoch) unless `--real-data`
+reads the `train` / `valid` image lists of `--data` through the device loader (utils/datasets.py: images cached on the GPU, letterbox
+and augmentation in one HIP launch per batch, csrc/augment.hip).  On a GPU the training-mode forward AND backward run the hand-written HIP
 TrainEngine (conv forward / dgrad / wgrad on MFMA, BatchNorm + PReLU kernels, fused loss, one-launch SGD;
 rotate-yolov3_amd/model/train_engine.py); CPU tensors and `--backend torch` (model.backend = 'torch') take the ATen operator chain --
 the way to train a "matrix" cfg (weight_from / d-convolutional layers), which the TrainEngine refuses; `--shared-conv hip` then runs
@@ -140,13 +141,25 @@ def train(opt, hyp):
         # the all-reduce delivers the SUM over ranks; FusedSGD applies 1/world while it reads the gradient (no extra 250 MB pass)
         optimizer.grad_scale = 1.0 / world
         dp.scale_in_optimizer = True
-    loader = SyntheticLoader(opt.synthetic, batch_size, opt.img_size, seed=rank, device=device)
+    valid_loader = None
+    if getattr(opt, 'real_data', False):
+        from rotate_yolov3_amd.utils.datasets import LoadImagesAndLabels
+        if not use_cuda:
+            raise RuntimeError("--real-data: the image cache and the letterbox / augmentation kernel live on a GPU; --device %r selects none" % opt.device)
+        data = parse_data_cfg(opt.data)
+        loader = LoadImagesAndLabels(data['train'], opt.img_size, batch_size, augment=True, hyp=hyp, rank=rank, world=world, device=device)
+        if not opt.notest and data.get('valid'):
+            valid_loader = LoadImagesAndLabels(data['valid'], opt.img_size, min(batch_size, 16), augment=False, device=device)
+    else:
+        loader = SyntheticLoader(opt.synthetic, batch_size, opt.img_size, seed=rank, device=device)
     nb = len(loader)
     results = (0, 0, 0, 0, 0, 0, 0)
     t0 = time.time()
     for epoch in range(start_epoch, epochs):
         model.train()
         set_epoch_lr(optimizer, hyp, epoch, epochs)
+        if hasattr(loader, 'set_epoch'):
+            loader.set_epoch(epoch)
         mloss = torch.zeros(4, device=device)
         s = ''
         for i, (imgs, targets, _, _) in enumerate(loader):
@@ -177,7 +190,7 @@ def train(opt, hyp):
                 with torch.no_grad():
                     results, _ = test_mod.test(opt.cfg, hyp, batch_size=min(batch_size, 16), img_size=opt.img_size, model=model,
                                                conf_thres=0.001 if final_epoch else 0.1, n_images=opt.test_images,
-                                               device=device)
+                                               device=device, loader=valid_loader)
                 model.train()
         if rank == 0:
             with open(results_file, 'a') as fh:
@@ -208,7 +221,7 @@ def make_parser():
     parser.add_argument('--accumulate', type=int, default=1, help='batches to accumulate before optimizing')
     parser.add_argument('--hyp', type=str, default='cfg/HRSC/hyp.py', help='hyper-parameter path')
     parser.add_argument('--cfg', type=str, default='cfg/HRSC/yolov3-416.cfg', help='cfg file path')
-    parser.add_argument('--data', type=str, default='data/hrsc.data', help='*.data file path (only `classes` is read)')
+    parser.add_argument('--data', type=str, default='data/hrsc.data', help='*.data file path (`classes`; with --real-data also the `train` / `valid` image lists)')
     parser.add_argument('--img-size', type=int, default=512, help='training size (pixels)')
     parser.add_argument('--resume', action='store_true', help='resume training from last.pt')
     parser.add_argument('--nosave', action='store_true', help='only save final checkpoint')
@@ -225,6 +238,9 @@ def make_parser():
     parser.add_argument('--test-images', type=int, default=32, help='synthetic images per evaluation')
     parser.add_argument('--wdir', default='weights')
     parser.add_argument('--synthetic', type=int, default=64, help='synthetic images per epoch per process')
+    parser.add_argument('--real-data', action='store_true',
+                        help="train on the `train` image list of --data (evaluate on its `valid` list) through the device loader "
+                             "instead of synthetic images; needs a GPU and Pillow")
     parser.add_argument('--bucket-mb', type=float, default=64.0, help='gradient all-reduce bucket size')
     parser.add_argument('--eager-loss', action='store_true', help='eager compute_loss mirror instead of the graph-captured loss')
     parser.add_argument('--backend', choices=['hip', 'torch'], default='hip',

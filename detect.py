@@ -1,8 +1,22 @@
 #!/usr/bin/env python
-"""detect.py -- inference entry point mirroring the reference's detect.py (detect() :142-275, flags :279-296):
+"""detect.py -- inference entry point mirroring the reference's detect.py (detect() :142-275, multi_detect() :16-137, flags :279-296):
 load cfg (+ .pt / darknet .weights), forward on the HIP engine, rotated NMS, write one text row per detection
-(x y w h angle score class).  Image decoding / letterboxing / ICDAR writers use OpenCV in the reference and are
-out of scope; the source here is a .pt/.npy tensor file [n,3,H,W] in [0,1] or `--synthetic N`."""
+(x y w h angle score class).
+
+--source is
+  * a directory of images, one image file or a .txt list of image paths: Pillow decodes, the original pixels go to the GPU once per
+    batch, ryolo_letterbox_area writes the letterboxed batch at the network size, and the rows are scaled back to the original image
+    (scale_coords(...).round()) on the device.  Per image: <output>/<stem>.txt.  --icdar adds <output>/icdar/res_<stem>.txt
+    (x0,y0,..,x3,y3 per detection) and <output>/icdar_result.zip of them.  --multi-scale runs every image at several sizes (--scales, or
+    two sizes drawn from the reference's range with --seed) and merges the rows with one more rotated NMS (multi_detect).
+    The zip holds the files of this run only; two images with the same stem are refused.
+  * a .npy / .pt tensor file [n,3,H,W] in [0,1], or anything that does not exist (`--synthetic N` random images): the tensor goes to
+    the model as it is and the rows (network coordinates) to <output>/img_%d.txt.  --multi-scale, --scales, --seed and --icdar have no
+    effect there and a NOTE says so.
+  * the exception to "anything that does not exist": a camera number (`0`), a stream URL (rtsp:// rtmp:// http:// https://) or a video
+    file that exists.  The reference opens these with OpenCV; here they are refused with a clear error instead of falling back to
+    synthetic images.
+Drawing the boxes into the images is out of scope."""
 import argparse
 import os
 import sys
@@ -20,6 +34,87 @@ from rotate_yolov3_amd.model.models import Darknet  # noqa: E402
 from rotate_yolov3_amd.utils.parse_config import hyp_parse  # noqa: E402
 
 
+def multi_scale_sizes(img_size, seed=0, size_num=2):
+    """the reference's draw (detect.py:55-58): size_num different multiples of 32 from
+    [(round(img_size / 32 / 1.5) + 1) * 32, (round(img_size / 32 * 1.3) - 1) * 32], here from a numpy Generator seeded by `seed`"""
+    lo, hi = multi_scale_range(img_size)
+    return [int(x) for x in np.random.default_rng(int(seed)).choice(np.arange(lo, hi + 32, 32), size_num, replace=False)]
+
+
+def multi_scale_range(img_size):
+    """(smallest, largest) size --multi-scale draws from"""
+    return (round(img_size / 32 / 1.5) + 1) * 32, (round(img_size / 32 * 1.3) - 1) * 32
+
+
+def parse_scales(text):
+    """'416,608,800' -> [416, 608, 800]: positive multiples of 32, no repeats"""
+    try:
+        sizes = [int(s) for s in str(text).split(',') if s.strip() != '']
+    except ValueError:
+        raise ValueError('--scales %r: a comma separated list of integers' % text)
+    if not sizes or any(s < 32 or s % 32 for s in sizes) or len(set(sizes)) != len(sizes):
+        raise ValueError('--scales %r: one or more different positive multiples of 32' % text)
+    return sizes
+
+
+def is_image_source(source):
+    """a directory, an image file or a .txt list that exists -- and a camera number, a stream URL or a video file that exists, which
+    LoadImages refuses with a clear error; tensor files and other paths that do not exist keep their old meaning"""
+    from rotate_yolov3_amd.utils.datasets import IMG_FORMATS, VID_FORMATS, is_video_or_stream
+    ext = os.path.splitext(source)[-1].lower()
+    if ext in ('.npy', '.pt'):
+        return False
+    if is_video_or_stream(source):       # a camera number, a URL, a video file that exists: LoadImages gives the clear error
+        return ext not in VID_FORMATS or os.path.isfile(source)
+    return os.path.isdir(source) or (os.path.isfile(source) and (ext in IMG_FORMATS or ext == '.txt'))
+
+
+def detect_image_files(model, opt, device):
+    """the image path: LoadImages -> detect_images per batch -> <stem>.txt (+ ICDAR rows); returns (images, detections)"""
+    from rotate_yolov3_amd.model import hip_ops
+    from rotate_yolov3_amd.utils.datasets import LoadImages
+    from rotate_yolov3_amd.utils.detect_images import detect_images
+    from rotate_yolov3_amd.utils.icdar import write_icdar, zip_files
+    sizes = [opt.img_size]
+    if getattr(opt, 'scales', ''):
+        sizes = parse_scales(opt.scales)
+    elif getattr(opt, 'multi_scale', False):
+        sizes = multi_scale_sizes(opt.img_size, getattr(opt, 'seed', 0))
+    if len(sizes) > 1 or getattr(opt, 'multi_scale', False):
+        print('use scale: {}'.format(sizes))
+    icdar = getattr(opt, 'icdar', False)
+    icdar_dir = os.path.join(opt.output, 'icdar')
+    if icdar:
+        os.makedirs(icdar_dir, exist_ok=True)
+    dataset = LoadImages(opt.source, opt.img_size, opt.batch_size, device)
+    stems = [os.path.splitext(os.path.basename(p))[0] for p in dataset.files]
+    twice = sorted(set(s for s in stems if stems.count(s) > 1))
+    if twice:
+        raise ValueError('detect.py: the result files are named by the image\'s stem, and %d stems occur more than once (%s ...): '
+                         'their results would overwrite each other' % (len(twice), twice[0]))
+    n_img = n_det = 0
+    icdar_files = []
+    for paths, cache, shapes in dataset:
+        n = len(paths)
+        out, det, det_off = detect_images(model, cache, n, shapes, sizes, opt.conf_thres, opt.nms_thres, slots=opt.batch_size)
+        quads = hip_ops.det_quads(det).cpu().tolist() if icdar else None
+        off = det_off.cpu().tolist()
+        rows = det.cpu().tolist()
+        for i, p in enumerate(paths):
+            stem = os.path.splitext(os.path.basename(p))[0]
+            with open(os.path.join(opt.output, stem + '.txt'), 'w') as f:
+                for *box, conf, _, cls in rows[off[i]:off[i + 1]]:
+                    f.write(('%g ' * 7 + '\n') % (*box, conf, cls))
+            if icdar:
+                icdar_files.append(write_icdar(icdar_dir, p, quads[off[i]:off[i + 1]]))
+        n_img += n
+        n_det += off[n]
+    if icdar:
+        # the files of this run only: the folder may hold res_*.txt of an earlier run with other images
+        zip_files(icdar_files, os.path.join(opt.output, 'icdar_result.zip'))
+    return n_img, n_det
+
+
 def detect(opt):
     device = getattr(opt, 'torch_device', None) or torch.device('cuda:0')
     hyp = hyp_parse(opt.hyp) if opt.hyp and os.path.isfile(opt.hyp) else {'context_factor': 1.0}
@@ -31,12 +126,23 @@ def detect(opt):
     elif opt.weights:
         load_darknet_weights(model, opt.weights)
     model.to(device).eval()
+    if is_image_source(opt.source):
+        os.makedirs(opt.output, exist_ok=True)
+        t0 = time.time()
+        n_img, n_det = detect_image_files(model, opt, device)
+        print('Done. %d images, %d detections (%.3fs)' % (n_img, n_det, time.time() - t0))
+        return
     if opt.source.endswith('.npy'):
         imgs = torch.from_numpy(np.load(opt.source)).float()
     elif opt.source.endswith('.pt'):
         imgs = torch.load(opt.source).float()
     else:
         imgs = torch.rand(opt.synthetic, 3, opt.img_size, opt.img_size, generator=torch.Generator().manual_seed(0))
+    given = [f for f, on in (('--multi-scale', getattr(opt, 'multi_scale', False)), ('--scales', getattr(opt, 'scales', '')),
+                             ('--seed', getattr(opt, 'seed', 0)), ('--icdar', getattr(opt, 'icdar', False))) if on]
+    if given:
+        print('NOTE: %s: only for a --source of image files (a directory, an image, a .txt list); no effect on %r'
+              % (', '.join(given), opt.source))
     os.makedirs(opt.output, exist_ok=True)
     t0 = time.time()
     n_det = 0
@@ -58,20 +164,23 @@ if __name__ == '__main__':
     parser.add_argument('--hyp', type=str, default='cfg/ICDAR/hyp.py', help='hyper-parameter path')
     parser.add_argument('--cfg', type=str, default='cfg/ICDAR/yolov3_608_dh_o8_ga.cfg', help='cfg file path')
     parser.add_argument('--weights', type=str, default='weights/last.pt', help='path to weights file (.pt or darknet .weights)')
-    parser.add_argument('--source', type=str, default='data/tiny/test', help='a .npy / .pt tensor file [n,3,H,W] in [0,1]; anything else: --synthetic random images (image decoding is out of scope)')
+    parser.add_argument('--source', type=str, default='data/tiny/test', help='a directory of images, an image file, a .txt list of image paths, or a .npy / .pt tensor file [n,3,H,W] in [0,1]; a path that does not exist: --synthetic random images')
     parser.add_argument('--output', type=str, default='output', help='output folder')
     parser.add_argument('--img-size', type=int, default=608, help='inference size (pixels)')
     parser.add_argument('--conf-thres', type=float, default=0.5, help='object confidence threshold')
     parser.add_argument('--nms-thres', type=float, default=0.3, help='iou threshold for non-maximum suppression')
     parser.add_argument('--device', default='', help='device id (i.e. 0 or 0,1); the detection path has no CPU fallback')
     parser.add_argument('--batch-size', type=int, default=8, help='images per forward')
-    parser.add_argument('--synthetic', type=int, default=8, help='random images when --source is not a tensor file')
+    parser.add_argument('--synthetic', type=int, default=8, help='random images when --source does not exist')
+    parser.add_argument('--multi-scale', action='store_true', help='multi-scale testing of image files: every image at several sizes, merged by one more rotated NMS')
+    parser.add_argument('--scales', type=str, default='', help='the sizes of multi-scale testing, e.g. 416,608,800 (multiples of 32); without it --multi-scale draws two sizes')
+    parser.add_argument('--seed', type=int, default=0, help='seed of the --multi-scale size draw')
+    parser.add_argument('--icdar', action='store_true', help='also write <output>/icdar/res_<stem>.txt and <output>/icdar_result.zip')
     ignored = add_ignored(parser, [
         ('--data', dict(type=str, default='data/tiny.data', help='*.data file path (class names for the image writers)')),
         ('--fourcc', dict(type=str, default='mp4v', help='output video codec')),
         ('--half', dict(action='store_true', help='half precision FP16 inference (the HIP engine always computes in bf16 with fp32 accumulation)')),
-        ('--view-img', dict(action='store_true', help='display results')),
-        ('--multi-scale', dict(action='store_true', help='multi-scale testing'))])
+        ('--view-img', dict(action='store_true', help='display results'))])
     opt = parser.parse_args()
     print(opt)
     report_ignored(parser, opt, ignored)

@@ -294,6 +294,42 @@ int ryolo_letterbox_augment(const uint8_t *pixels, const long long *img_offset, 
                             const int *src_index /* [N] */, const float *params /* [N][16] */, long long seed, int N, int H, int W,
                             void *y /* bf16 [N][H][W][8] */, void *stream);
 
+/* Detection input (csrc/letterbox_area.hip) -- letterbox(img0, new_shape) of the reference's detect.py (utils/datasets.py:431-451) on the
+ * device, from the ORIGINAL pixels to any size: the cache layout, src_index and the output (bf16 [N][H][W][8], channels 3..7 zero, one
+ * 16-byte store per pixel) are those of ryolo_letterbox_augment; a src_index outside [0, n_cache) makes the slot all border.
+ *   place       HOST memory, [N][4] rows (left, top, new_w, new_h): slot n shows its image resized to new_w x new_h with the top left
+ *               corner at output pixel (left, top).  Read and validated during the call and passed on in the kernel arguments (64 slots per
+ *               launch), so a captured graph replays the rows it was captured with.
+ * Output pixel (x, y) with left <= x < left + new_w and top <= y < top + new_h is inside the picture; every other one is 128 exactly (a
+ * hard edge, as cv2.copyMakeBorder makes).  Inside, the value is the separable sum  (sum_j Wy_j ((sum_i Wx_i p[j][i]) / Dx)) / Dy  per
+ * channel, with integer weights per axis (source length s, output length n, output index k):
+ *   n <  s   exact coverage: taps i from (k s) div n while i n < (k + 1) s, W = min((k + 1) s, (i + 1) n) - max(k s, i n), D = s (64-bit);
+ *   n >= s   bilinear with aligned pixel centres: c = (2 k + 1) s - n, q = floor(c / 2n), r = c - 2n q; taps q, q + 1 clamped to
+ *            [0, s - 1], W = (2n - r, r), D = 2n; n == s is the pixel itself.
+ * fp32 on a 0..255 scale, sums from the first tap up, no uint8 rounding; then c / 255.0f (a division) and round to nearest even bf16.  The
+ * full definition is the header comment of csrc/letterbox_area.hip; tests/letterbox_area_reference.py restates it in float64.
+ * ceil(N / 64) launches on `stream`: 256-thread workgroups own 32 x 32 output tiles; no workspace, no allocation, no atomics, one writer
+ * per element, capture-safe, bit-identical from run to run.  RYOLO_EINVAL before any HIP call: a null pointer (other than stream), N, H, W
+ * or n_cache < 1, N or the row-tile count above 65535, y not 16-byte aligned, a place row with new_w or new_h < 1 or whose rectangle is
+ * not inside H x W. */
+int ryolo_letterbox_area(const uint8_t *pixels, const long long *img_offset, const int *img_hw /* [n_cache][2] */, int n_cache,
+                         const int *src_index /* [N] */, const int *place /* host [N][4]: left, top, new_w, new_h */, int N, int H, int W,
+                         void *y /* bf16 [N][H][W][8] */, void *stream);
+
+/* Detection output (csrc/detpost.hip) -- what the reference's detect.py does to every detection in Python, one launch per batch each.
+ * Both make no launch and return RYOLO_OK when M == 0; both are capture-safe, without workspace or atomics.
+ * ryolo_det_rescale: scale_coords(...).round() (utils/utils.py:181-189) in place on flat rows [M][8]: row r belongs to image b with
+ *   det_off[b] <= r < det_off[b + 1]; geom[b] = (gain, pad_x, pad_y) -- gain = S / max(h0, w0), pad_x = (S - w0 gain) / 2, pad_y alike,
+ *   computed by the host in double and stored as fp32.  Columns 0, 1 become rintf((v - pad) / gain), columns 2, 3 rintf(v / gain), a
+ *   true fp32 division; columns 4..7 are untouched.
+ * ryolo_det_quads: xywha2icdar (utils/ICDAR/icdar_utils.py:105-135) per row in fp64 -- the four corners turned by cos(-a), sin(-a),
+ *   order_points (stable sort by x; the two left-most by y are tl, bl; of the two right-most the one farther from tl is br, on a tie the
+ *   later one), then tl, tr, br, bl truncated toward zero to int32.
+ * RYOLO_EINVAL: M < 0, bs < 1, and for M > 0 a null pointer (other than stream) or det / quad not 16-byte aligned. */
+int ryolo_det_rescale(float *det /* [M][8], in place */, int M, const int *det_off /* [bs+1], device */, int bs,
+                      const float *geom /* [bs][3]: gain, pad_x, pad_y, device */, void *stream);
+int ryolo_det_quads(const float *det /* [M][8] */, int M, int *quad /* [M][8] */, void *stream);
+
 
 /* Decode + score filter + compaction (no `io` tensor): the rows of ryolo_yolo_decode's `io` that the first half of
  * non_max_suppression keeps (utils/nms/nms.py:33-48: class_conf/class = max over io[6:], score = io[5]*class_conf,

@@ -263,6 +263,86 @@ def letterbox_augment(cache, src_index, params, seed, H, W, out=None):
     return NHWC8Batch(out)
 
 
+def letterbox_area(cache, src_index, place, H, W, out=None):
+    """ceil(N / 64) launches of csrc/letterbox_area.hip: batch slot n = the cached image src_index[n] resized to place[n][2:] (area
+    averaging when that is smaller, bilinear otherwise) with its top left corner at place[n][:2], 128 around it (include/ryolo.h:
+    ryolo_letterbox_area) -> NHWC8Batch of [N, H, W, 8].
+    cache: as for letterbox_augment; src_index: int32 [N] on the cache's device; place: [N, 4] integer rows (left, top, new_w, new_h) on the
+    HOST (a numpy array, a list, a CPU tensor: utils.datasets.place_rows); out: a bf16 [N, H, W, 8] tensor to write into."""
+    import numpy as np
+    from .nhwc_batch import NHWC8Batch
+    L = _lib.lib()
+    pixels, offs, hw = cache.pixels, cache.img_offset, cache.img_hw
+    dev = pixels.device
+    if not (pixels.is_cuda and pixels.dtype == torch.uint8 and pixels.is_contiguous()):
+        raise RuntimeError("cache.pixels must be a contiguous uint8 GPU tensor")
+    n_cache = offs.numel()
+    if not (offs.dtype == torch.int64 and offs.is_contiguous() and offs.device == dev and hw.dtype == torch.int32 and hw.is_contiguous()
+            and hw.device == dev and tuple(hw.shape) == (n_cache, 2)):
+        raise RuntimeError("cache.img_offset / cache.img_hw must be int64 [n] / int32 [n, 2] tensors on the cache's device")
+    if not torch.is_tensor(src_index):
+        src_index = torch.tensor(list(src_index), dtype=torch.int32, device=dev)
+    n = src_index.numel()
+    if not (src_index.dtype == torch.int32 and src_index.dim() == 1 and src_index.is_contiguous() and src_index.device == dev):
+        raise RuntimeError("src_index must be a contiguous int32 [N] tensor on the cache's device")
+    if torch.is_tensor(place):
+        if place.is_cuda or place.is_floating_point():
+            raise RuntimeError("place must be integer [N, 4] rows in host memory, not a %s tensor on %s" % (place.dtype, place.device))
+        place = place.numpy()
+    place = np.asarray(place)
+    if not (place.dtype.kind in 'iu' and place.shape == (n, 4)):
+        raise RuntimeError("place must be integer [N, 4] rows (left, top, new_w, new_h), not %s %s" % (place.dtype, place.shape))
+    place = np.ascontiguousarray(place, dtype=np.int32)
+    if out is None:
+        out = torch.empty((n, H, W, 8), dtype=torch.bfloat16, device=dev)
+    elif not (out.dtype == torch.bfloat16 and out.is_contiguous() and out.device == dev and tuple(out.shape) == (n, H, W, 8)):
+        raise RuntimeError("out must be a contiguous bf16 [N, H, W, 8] tensor on the cache's device")
+    with torch.cuda.device(dev):
+        _lib.check(L.ryolo_letterbox_area(pixels.data_ptr(), offs.data_ptr(), hw.data_ptr(), n_cache, src_index.data_ptr(),
+                                          place.ctypes.data, n, int(H), int(W), out.data_ptr(), _lib.stream_ptr(dev)),
+                   "ryolo_letterbox_area")
+    return NHWC8Batch(out)
+
+
+def _check_det(det):
+    if not (torch.is_tensor(det) and det.is_cuda and det.dtype == torch.float32 and det.dim() == 2 and det.shape[1] == 8
+            and det.is_contiguous()):
+        raise RuntimeError("det must be a contiguous fp32 [M, 8] GPU tensor")
+
+
+def det_rescale(det, det_off, geom):
+    """scale_coords(...).round() of the reference in place on the flat detection rows of a batch (include/ryolo.h: ryolo_det_rescale).
+    det: fp32 [M, 8]; det_off: int32 [bs + 1] row offsets per image; geom: fp32 [bs, 3] rows (gain, pad_x, pad_y)
+    (utils.detect_images.rescale_geometry), all on one GPU.  Returns det."""
+    _check_det(det)
+    dev = det.device
+    if not (torch.is_tensor(det_off) and det_off.dtype == torch.int32 and det_off.dim() == 1 and det_off.numel() >= 2
+            and det_off.is_contiguous() and det_off.device == dev):
+        raise RuntimeError("det_off must be a contiguous int32 [bs + 1] tensor on det's device")
+    bs = det_off.numel() - 1
+    if not (torch.is_tensor(geom) and geom.dtype == torch.float32 and geom.is_contiguous() and geom.device == dev
+            and tuple(geom.shape) == (bs, 3)):
+        raise RuntimeError("geom must be a contiguous fp32 [bs, 3] tensor on det's device")
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().ryolo_det_rescale(det.data_ptr(), det.shape[0], det_off.data_ptr(), bs, geom.data_ptr(),
+                                                _lib.stream_ptr(dev)), "ryolo_det_rescale")
+    return det
+
+
+def det_quads(det, out=None):
+    """xywha2icdar of the reference for every row of det (fp32 [M, 8]) -> int32 [M, 8] rows (x, y of tl, tr, br, bl)
+    (include/ryolo.h: ryolo_det_quads)."""
+    _check_det(det)
+    dev = det.device
+    if out is None:
+        out = torch.empty((det.shape[0], 8), dtype=torch.int32, device=dev)
+    elif not (out.dtype == torch.int32 and out.is_contiguous() and out.device == dev and tuple(out.shape) == (det.shape[0], 8)):
+        raise RuntimeError("out must be a contiguous int32 [M, 8] tensor on det's device")
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().ryolo_det_quads(det.data_ptr(), det.shape[0], out.data_ptr(), _lib.stream_ptr(dev)), "ryolo_det_quads")
+    return out
+
+
 def nhwc_bf16_to_nchw_f32(x):
     cs = _check_nhwc(x, "x")
     n, h, w, c = x.shape

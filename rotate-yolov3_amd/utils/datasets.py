@@ -341,3 +341,96 @@ class LoadImagesAndLabels(object):
                                               torch.from_numpy(rows).to(self.device), noise_seed, S, S)
             yield (batch, torch.from_numpy(np.concatenate(targets, 0)).to(self.device), tuple(self.img_files[i] for i in chunk),
                    tuple(self.cache.shapes[i] for i in chunk))
+
+
+VID_FORMATS = ('.mov', '.avi', '.mp4', '.mpg', '.mpeg', '.m4v', '.wmv', '.mkv')
+
+
+def place_rows(shapes, size):
+    """the int32 [N, 4] rows (left, top, new_w, new_h) of ryolo_letterbox_area: where letterbox_matrix puts each (h, w) image of `shapes`
+    in a size x size batch.  A side that would round to 0 pixels is 1 (cv2.resize of the reference fails there)."""
+    rows = np.empty((len(shapes), 4), dtype=np.int32)
+    for k, (h, w) in enumerate(shapes):
+        lb = letterbox_matrix(h, w, size)
+        new_w, new_h = max(lb.new_unpad[0], 1), max(lb.new_unpad[1], 1)
+        rows[k] = (min(lb.left, size - new_w), min(lb.top, size - new_h), new_w, new_h)
+    return rows
+
+
+def is_video_or_stream(path):
+    """a camera number, a stream URL or a path with a video extension: what the reference hands to cv2.VideoCapture"""
+    path = str(path)
+    return (path.isdigit() or path.startswith(('rtsp://', 'rtmp://', 'http://', 'https://'))
+            or os.path.splitext(path)[-1].lower() in VID_FORMATS)
+
+
+def list_images(path):
+    """the image files `path` names: a directory (sorted, filtered by IMG_FORMATS), one image file, or a .txt list of paths"""
+    path = str(path)
+    ext = os.path.splitext(path)[-1].lower()
+    if is_video_or_stream(path):
+        raise NotImplementedError("LoadImages: %r is a video or a stream; this port decodes still images with Pillow and has no OpenCV "
+                                  "(extract the frames to a directory of images)" % path)
+    if os.path.isdir(path):
+        names = sorted(os.listdir(path))
+        videos = [x for x in names if os.path.splitext(x)[-1].lower() in VID_FORMATS]
+        if videos:
+            raise NotImplementedError("LoadImages: %s holds video files (%s ...); this port decodes still images with Pillow and has no "
+                                      "OpenCV" % (path, videos[0]))
+        files = [os.path.join(path, x) for x in names if os.path.splitext(x)[-1].lower() in IMG_FORMATS]
+    elif ext == '.txt' and os.path.isfile(path):
+        with open(path, 'r') as f:
+            files = [x.strip().replace('/', os.sep) for x in f.read().splitlines()]
+        files = [x for x in files if os.path.splitext(x)[-1].lower() in IMG_FORMATS]
+    elif ext in IMG_FORMATS and os.path.isfile(path):
+        files = [path]
+    else:
+        raise FileNotFoundError("LoadImages: %r is neither a directory, an image file %s nor a .txt list" % (path, IMG_FORMATS))
+    if not files:
+        raise ValueError('No images found in %s' % path)
+    return files
+
+
+class LoadImages(object):
+    """The reference's inference loader (utils/datasets.py LoadImages) on the device path.  Per batch of batch_size files Pillow decodes to
+    RGB and the ORIGINAL pixels are uploaded once (DeviceImageCache.from_arrays): nothing is resized on the host, ryolo_letterbox_area
+    writes the batch at whatever size is asked for.  Yields (paths, cache, shapes): the files of the batch, their device cache, their
+    (h, w).  letterbox_batch(cache, shapes, size, slots=batch_size) makes the NHWC8Batch: always batch_size slots, so one engine shape
+    serves the whole run; the slots past the images (the last batch) have src_index -1, are all border, and their results are dropped.
+    img_size is the reference's argument and is only kept (.img_size): the loader resizes nothing, the size is letterbox_batch's."""
+
+    def __init__(self, path, img_size=416, batch_size=8, device='cuda'):
+        self.files = list_images(path)
+        self.img_size, self.batch_size, self.device = int(img_size), int(batch_size), torch.device(device)
+        if self.batch_size < 1:
+            raise ValueError('batch_size %d' % self.batch_size)
+
+    def __len__(self):
+        return (len(self.files) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        try:
+            from PIL import Image
+        except ImportError:
+            raise RuntimeError("LoadImages decodes images with Pillow, which is not installed (pip install pillow)")
+        for b in range(0, len(self.files), self.batch_size):
+            paths = tuple(self.files[b:b + self.batch_size])
+            arrays = []
+            for p in paths:
+                with Image.open(p) as im:
+                    arrays.append(np.asarray(im.convert('RGB'), dtype=np.uint8))
+            cache = DeviceImageCache.from_arrays(arrays, self.device)
+            yield paths, cache, tuple(cache.hw)
+
+
+def letterbox_batch(cache, shapes, size, slots=None, out=None):
+    """ryolo_letterbox_area of the len(shapes) images of `cache` into `slots` >= len(shapes) slots of size x size; the slots past the
+    images read nothing (src_index -1)"""
+    from ..model import hip_ops
+    n = len(shapes)
+    slots = n if slots is None else int(slots)
+    if slots < n:
+        raise ValueError('%d images do not fit %d slots' % (n, slots))
+    src = torch.tensor(list(range(n)) + [-1] * (slots - n), dtype=torch.int32).to(cache.pixels.device)
+    place = np.concatenate((place_rows(shapes, size), np.tile(np.array([[0, 0, 1, 1]], dtype=np.int32), (slots - n, 1))), 0)
+    return hip_ops.letterbox_area(cache, src, place, size, size, out)

@@ -695,6 +695,28 @@ typedef struct ryolo_sgd_job {
 int ryolo_sgd_step(const ryolo_sgd_job *device_jobs, int njobs, int total_blocks, const float *group_hparams, int nesterov,
                    void *stream);
 
+/* The Adam step of train.py:77-82 (`--adam`: torch.optim.Adam, amsgrad = maximize = False, L2 weight decay per group) for every
+ * parameter tensor in one launch.  jobs: device array, one per tensor that has a gradient (fp32 p / grad / exp_avg / exp_avg_sq,
+ * n elements, `row` = its row of the table below, [block_begin, block_end) = its workgroup range, ascending and gap-free over
+ * the jobs; total_blocks = the last block_end).  A tensor whose four pointers are 16-byte aligned moves 16 bytes per lane, any
+ * other 4 (gradients that are views into a flat bucket); both give the same bits.
+ * rows: device float[rows][8] = (step_size = -lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), 1 - beta1, beta2, 1 - beta2, eps,
+ * weight_decay, gradient scale; 0 = no scaling, as in ryolo_sgd_step), computed by the caller in doubles and rounded to fp32.
+ * One row per (param group, step count t): torch counts steps per parameter, and one that had no gradient for a while lags behind.
+ * Per element, in torch.optim.Adam's operator order and fp32 (IEEE sqrt and divide, no contraction):
+ *   d = g (* scale) (+ weight_decay * p);  m += (1 - beta1) * (d - m);  v = v * beta2 + ((1 - beta2) * d) * d;
+ *   p += step_size * (m / (sqrt(v) / bc2_sqrt + eps)).
+ * Only enqueues.  RYOLO_EINVAL: a null table or njobs / total_blocks <= 0. */
+typedef struct ryolo_adam_job {
+    void *p;
+    const void *g;
+    void *m;
+    void *v;
+    long long n;
+    int row, block_begin, block_end;
+} ryolo_adam_job;
+int ryolo_adam_step(const ryolo_adam_job *device_jobs, int njobs, int total_blocks, const float *rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

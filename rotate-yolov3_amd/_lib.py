@@ -2,7 +2,7 @@
 
 The header is the only place a signature is written: importing this module parses it (no library needed) into `_sigs`,
 entry point -> (restype, argtypes) for every prototype, and into the ctypes.Structure classes of its `typedef struct`s
-(ConvDesc, PackJob, WgradReduceJob, SgdJob); lib() applies the whole table when it loads the library.  A type the parser
+(ConvDesc, PackJob, WgradReduceJob, SgdJob, AdamJob); lib() applies the whole table when it loads the library.  A type the parser
 has no mapping for fails the import -- nothing is guessed, nothing is left to ctypes' default of passing a C int.
 
 The library is built in-tree by __graft_entry__.build() (hipcc --offload-arch=gfx950).  There is NO fallback:
@@ -89,6 +89,7 @@ with open(os.path.join(_HERE, os.pardir, "include", "ryolo.h")) as _fh:
     _structs, _sigs = _parse_header(_fh.read())      # _sigs: entry point -> (restype, argtypes), every prototype of the header
 ConvDesc, PackJob = _structs["ryolo_conv_desc"], _structs["ryolo_pack_job"]
 WgradReduceJob, SgdJob = _structs["ryolo_wgrad_reduce_job"], _structs["ryolo_sgd_job"]
+AdamJob = _structs["ryolo_adam_job"]
 
 
 def lib():

@@ -56,7 +56,7 @@ def main():
             step()
         torch.cuda.synchronize()
     # device-side view: every kernel / copy of the two steps that is NOT one of the library's own kernels
-    ours = ("ryolo", "conv_", "wgrad", "bn_act", "bn_finalize", "yolo_", "sgd_batch", "pack_batch", "build_targets", "nchw_f32", "upsample", "add_nhwc",
+    ours = ("ryolo", "conv_", "wgrad", "bn_act", "bn_finalize", "yolo_", "sgd_batch", "adam_batch", "pack_batch", "build_targets", "nchw_f32", "upsample", "add_nhwc",
             "riou", "dgrad3x3", "conv0_", "conv3x3", "pgrad")
     dev_rows = {}
     for ev in prof.events():

@@ -10,7 +10,7 @@ train.py ...`) with bucketed RCCL all-reduce overlapped with backward (rotate-yo
 reference's broken single-process DDP; the input pipeline is synthetic (`--synthetic N` images per epoch) unless `--real-data`
 reads the `train` / `valid` image lists of `--data` through the device loader (utils/datasets.py: images cached on the GPU, letterbox
 and augmentation in one HIP launch per batch, csrc/augment.hip).  On a GPU the training-mode forward AND backward run the hand-written HIP
-TrainEngine (conv forward / dgrad / wgrad on MFMA, BatchNorm + PReLU kernels, fused loss, one-launch SGD;
+TrainEngine (conv forward / dgrad / wgrad on MFMA, BatchNorm + PReLU kernels, fused loss, one-launch SGD or Adam;
 rotate-yolov3_amd/model/train_engine.py); CPU tensors and `--backend torch` (model.backend = 'torch') take the ATen operator chain --
 the way to train a "matrix" cfg (weight_from / d-convolutional layers), which the TrainEngine refuses; `--shared-conv hip` then runs
 its dilated shared 3x3 layers on the HIP kernels (model.shared_conv_backend, hip_train_ops.SharedDilatedConv).  The se cfgs train the
@@ -48,9 +48,13 @@ def make_optimizer(model, hyp, adam=False, fused=True):
     pg0, pg1 = [], []
     for k, v in dict(model.named_parameters()).items():
         (pg1 if 'Conv2d.weight' in k else pg0).append(v)
-    if adam:
+    fused = fused and all(p.is_cuda and p.dtype == torch.float32 for p in pg0 + pg1)
+    if adam and fused:
+        from rotate_yolov3_amd.utils.fused_adam import FusedAdam    # same arithmetic, one launch for all parameter tensors
+        optimizer = FusedAdam(pg0, lr=hyp['lr0'])
+    elif adam:
         optimizer = optim.Adam(pg0, lr=hyp['lr0'])
-    elif fused and all(p.is_cuda and p.dtype == torch.float32 for p in pg0 + pg1):
+    elif fused:
         from rotate_yolov3_amd.utils.fused_sgd import FusedSGD      # same arithmetic, one launch for all 222 tensors
         optimizer = FusedSGD(pg0, lr=hyp['lr0'], momentum=hyp['momentum'], nesterov=True)
     else:
@@ -138,7 +142,7 @@ def train(opt, hyp):
     dp = GradientAllReducer(model, bucket_mb=opt.bucket_mb)
     init_schedule(optimizer, hyp)         # after load_state_dict: base lr = lr0, not the saved (already scaled) lr
     if world > 1 and hasattr(optimizer, 'grad_scale'):
-        # the all-reduce delivers the SUM over ranks; FusedSGD applies 1/world while it reads the gradient (no extra 250 MB pass)
+        # the all-reduce delivers the SUM over ranks; FusedSGD / FusedAdam apply 1/world while they read the gradient (no extra 250 MB pass)
         optimizer.grad_scale = 1.0 / world
         dp.scale_in_optimizer = True
     valid_loader = None

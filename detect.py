@@ -10,13 +10,19 @@ load cfg (+ .pt / darknet .weights), forward on the HIP engine, rotated NMS, wri
     (x0,y0,..,x3,y3 per detection) and <output>/icdar_result.zip of them.  --multi-scale runs every image at several sizes (--scales, or
     two sizes drawn from the reference's range with --seed) and merges the rows with one more rotated NMS (multi_detect).
     The zip holds the files of this run only; two images with the same stem are refused.
+    --save-img adds the picture itself, <output>/<name of the image file>, with every detection drawn into it as the reference's
+    plot_one_box does: the rotated outline (ryolo_det_corners + ryolo_draw_quads on the original pixels, on the device; thickness
+    round(0.002 (h + w) / 2) + 1 or --line-thickness) and the label '<class name> <score>' at the box's first corner, in the class's colour.
+    The class names come from the `names` file of --data.  One download per batch; the files are encoded by a pool of threads (PNG stays
+    PNG, JPEG at quality 95).  An --output that is the folder an image is read from is refused: the pictures would overwrite their sources.
   * a .npy / .pt tensor file [n,3,H,W] in [0,1], or anything that does not exist (`--synthetic N` random images): the tensor goes to
-    the model as it is and the rows (network coordinates) to <output>/img_%d.txt.  --multi-scale, --scales, --seed and --icdar have no
-    effect there and a NOTE says so.
+    the model as it is and the rows (network coordinates) to <output>/img_%d.txt.  --multi-scale, --scales, --seed, --icdar, --save-img and
+    --line-thickness have no effect there and a NOTE says so.
   * the exception to "anything that does not exist": a camera number (`0`), a stream URL (rtsp:// rtmp:// http:// https://) or a video
     file that exists.  The reference opens these with OpenCV; here they are refused with a clear error instead of falling back to
     synthetic images.
-Drawing the boxes into the images is out of scope."""
+The outline is this port's own exact definition (include/ryolo.h: ryolo_draw_quads), not cv2.polylines pixel for pixel; the label is
+upright.  Displaying the pictures (--view-img) and video output are out of scope."""
 import argparse
 import os
 import sys
@@ -69,8 +75,28 @@ def is_image_source(source):
     return os.path.isdir(source) or (os.path.isfile(source) and (ext in IMG_FORMATS or ext == '.txt'))
 
 
+def check_save_img_output(opt):
+    """--save-img writes <output>/<name of the image file>: refuse an output folder that an image would be read from"""
+    from rotate_yolov3_amd.utils.datasets import list_images
+    out = os.path.realpath(opt.output)
+    for p in list_images(opt.source):
+        if os.path.realpath(os.path.dirname(os.path.abspath(p))) == out:
+            raise ValueError('detect.py --save-img: --output %r is the folder %r is read from: the drawn pictures would overwrite their '
+                             'sources; choose another --output' % (opt.output, p))
+
+
+def class_names(opt):
+    """the class names of --data for the labels; without the files a NOTE, and the labels carry class indices"""
+    from rotate_yolov3_amd.utils.plots import load_class_names
+    data = getattr(opt, 'data', '')
+    names = load_class_names(data)
+    if names is None:
+        print('NOTE: --data %r: no *.data file with a `names` file there: the labels carry class indices' % data)
+    return names
+
+
 def detect_image_files(model, opt, device):
-    """the image path: LoadImages -> detect_images per batch -> <stem>.txt (+ ICDAR rows); returns (images, detections)"""
+    """the image path: LoadImages -> detect_images per batch -> <stem>.txt (+ ICDAR rows, + the drawn pictures); returns (images, detections)"""
     from rotate_yolov3_amd.model import hip_ops
     from rotate_yolov3_amd.utils.datasets import LoadImages
     from rotate_yolov3_amd.utils.detect_images import detect_images
@@ -92,6 +118,15 @@ def detect_image_files(model, opt, device):
     if twice:
         raise ValueError('detect.py: the result files are named by the image\'s stem, and %d stems occur more than once (%s ...): '
                          'their results would overwrite each other' % (len(twice), twice[0]))
+    save_img = getattr(opt, 'save_img', False)
+    if save_img:
+        from concurrent.futures import ThreadPoolExecutor
+        from rotate_yolov3_amd.utils import plots
+        names = class_names(opt)
+        colors = plots.class_colors(len(names) if names else plots.DEFAULT_CLASSES)
+        thick = int(getattr(opt, 'line_thickness', 0) or 0) or None
+        pool = ThreadPoolExecutor(max_workers=max(1, min(8, opt.batch_size, os.cpu_count() or 1)))
+        pending = []                     # the encodings in flight, a list per batch: at most two batches' pixels are held
     n_img = n_det = 0
     icdar_files = []
     for paths, cache, shapes in dataset:
@@ -107,8 +142,25 @@ def detect_image_files(model, opt, device):
                     f.write(('%g ' * 7 + '\n') % (*box, conf, cls))
             if icdar:
                 icdar_files.append(write_icdar(icdar_dir, p, quads[off[i]:off[i + 1]]))
+        if save_img:
+            # the boxes and labels are painted on the device; ONE download of the batch's pixels, the encoders work on views of it
+            drawn = plots.draw_detections(cache, n, det, det_off, names, colors, thick, host_rows=rows).cpu().numpy()
+            while len(pending) > 1:
+                for f in pending.pop(0):
+                    f.result()           # an encoder's error is the run's error
+            pending.append([])
+            at = 0
+            for p, (h, w) in zip(paths, cache.hw):
+                pending[-1].append(pool.submit(plots.save_image, drawn[at:at + 3 * h * w].reshape(h, w, 3),
+                                               os.path.join(opt.output, os.path.basename(p))))
+                at += 3 * h * w
         n_img += n
         n_det += off[n]
+    if save_img:
+        pool.shutdown(wait=True)
+        for batch in pending:
+            for f in batch:
+                f.result()
     if icdar:
         # the files of this run only: the folder may hold res_*.txt of an earlier run with other images
         zip_files(icdar_files, os.path.join(opt.output, 'icdar_result.zip'))
@@ -116,6 +168,8 @@ def detect_image_files(model, opt, device):
 
 
 def detect(opt):
+    if getattr(opt, 'save_img', False) and is_image_source(opt.source):
+        check_save_img_output(opt)       # before anything is loaded or written
     device = getattr(opt, 'torch_device', None) or torch.device('cuda:0')
     hyp = hyp_parse(opt.hyp) if opt.hyp and os.path.isfile(opt.hyp) else {'context_factor': 1.0}
     model = Darknet(opt.cfg, hyp)
@@ -139,7 +193,8 @@ def detect(opt):
     else:
         imgs = torch.rand(opt.synthetic, 3, opt.img_size, opt.img_size, generator=torch.Generator().manual_seed(0))
     given = [f for f, on in (('--multi-scale', getattr(opt, 'multi_scale', False)), ('--scales', getattr(opt, 'scales', '')),
-                             ('--seed', getattr(opt, 'seed', 0)), ('--icdar', getattr(opt, 'icdar', False))) if on]
+                             ('--seed', getattr(opt, 'seed', 0)), ('--icdar', getattr(opt, 'icdar', False)),
+                             ('--save-img', getattr(opt, 'save_img', False)), ('--line-thickness', getattr(opt, 'line_thickness', 0))) if on]
     if given:
         print('NOTE: %s: only for a --source of image files (a directory, an image, a .txt list); no effect on %r'
               % (', '.join(given), opt.source))
@@ -176,14 +231,18 @@ if __name__ == '__main__':
     parser.add_argument('--scales', type=str, default='', help='the sizes of multi-scale testing, e.g. 416,608,800 (multiples of 32); without it --multi-scale draws two sizes')
     parser.add_argument('--seed', type=int, default=0, help='seed of the --multi-scale size draw')
     parser.add_argument('--icdar', action='store_true', help='also write <output>/icdar/res_<stem>.txt and <output>/icdar_result.zip')
+    parser.add_argument('--save-img', action='store_true', help='image files only: also write <output>/<image name>, the picture with the boxes and labels drawn in (on the device)')
+    parser.add_argument('--line-thickness', type=int, default=0, help='outline thickness of --save-img in pixels, 1..255 (0: round(0.002 (h + w) / 2) + 1 per image)')
     ignored = add_ignored(parser, [
-        ('--data', dict(type=str, default='data/tiny.data', help='*.data file path (class names for the image writers)')),
+        ('--data', dict(type=str, default='data/tiny.data', help='*.data file path: with --save-img its `names` file names the classes in the labels')),
         ('--fourcc', dict(type=str, default='mp4v', help='output video codec')),
         ('--half', dict(action='store_true', help='half precision FP16 inference (the HIP engine always computes in bf16 with fp32 accumulation)')),
         ('--view-img', dict(action='store_true', help='display results'))])
     opt = parser.parse_args()
     print(opt)
-    report_ignored(parser, opt, ignored)
+    report_ignored(parser, opt, [n for n in ignored if not (n == 'data' and opt.save_img)])     # --save-img reads --data
+    if not 0 <= opt.line_thickness <= 255:
+        parser.error('--line-thickness %d: 1..255, or 0 for the default' % opt.line_thickness)
     opt.torch_device = pick_device(opt.device)
     if opt.torch_device.type != 'cuda':
         sys.exit('detect.py: the detection path (HIP forward + rotated NMS) needs a GPU; --device %r selects none' % opt.device)

@@ -329,6 +329,40 @@ int ryolo_letterbox_area(const uint8_t *pixels, const long long *img_offset, con
 int ryolo_det_rescale(float *det /* [M][8], in place */, int M, const int *det_off /* [bs+1], device */, int bs,
                       const float *geom /* [bs][3]: gain, pad_x, pad_y, device */, void *stream);
 int ryolo_det_quads(const float *det /* [M][8] */, int M, int *quad /* [M][8] */, void *stream);
+/* ryolo_det_corners: get_rotated_coors (utils/utils.py:702-725) per row in fp64 -- the arithmetic of ryolo_det_quads up to, but not
+ *   including, order_points: the corners (xmin, ymin), (xmin, ymax), (xmax, ymax), (xmax, ymin) turned by cos(-a), sin(-a), kept in THAT
+ *   order (a cycle; corner 0 anchors the drawn label) and truncated toward zero to int32, as .astype(np.int32) truncates.  The outline
+ *   ryolo_draw_quads draws.  Arguments, M == 0 and capture safety as for ryolo_det_quads. */
+int ryolo_det_corners(const float *det /* [M][8] */, int M, int *quad /* [M][8] */, void *stream);
+
+/* Drawing (csrc/draw.hip) -- plot_one_box / plot_images of the reference (utils/utils.py:479-490, :514-550) on the device: rotated
+ * outlines and label bitmaps painted into the pixels of an image cache (uint8 RGB HWC, image b at img_offset[b] bytes, img_hw[b] = (h, w)).
+ * Row r of quad / color / lab_* belongs to image b with det_off[b] <= r < det_off[b + 1].  The three bytes of pixel P = (x, y) of image b in
+ * dst are color[r*], r* the LARGEST row of the image that covers P (later rows paint over earlier ones); with no such row, those of src.
+ *   outline  Q0..Q3 = quad[r] (ryolo_det_corners), t = thick[b].  r covers P when for an edge A = Qk, B = Q(k+1 mod 4) the squared distance
+ *            from P to the closed segment AB has 4 dist^2 <= t^2, in exact integers: d = B - A, L2 = d.d, u = (P - A).d;  u <= 0 or L2 = 0:
+ *            4 |P - A|^2 <= t^2;  u >= L2: 4 |P - B|^2 <= t^2;  else c = (P - A) x d and 4 c^2 <= t^2 L2.  A thick polyline with round
+ *            joints and caps of diameter t; t = 1 leaves no gap in any line.  This definition is the port's own: cv2.polylines is not
+ *            matched pixel for pixel.  A row with a corner coordinate outside [-16384, 32767] draws nothing, its label neither.
+ *   label    lab_rect[r] = (lx, ly, lw, lh): r covers P when lx <= x < lx + lw, ly <= y < ly + lh and
+ *            lab_bits[lab_off[r] + (y - ly) lw + (x - lx)] != 0 -- one byte per label pixel; the rectangle may lie partly or wholly outside
+ *            the image; lw = 0 or lh = 0: no label for the row.  All three label pointers NULL: no labels at all.
+ *   thick    HOST memory, [n_img], each 1..255: read and validated during the call and passed on in the kernel arguments, so a captured
+ *            graph replays the thicknesses it was captured with (like `place` of ryolo_letterbox_area).
+ *   max_h, max_w   at least the largest img_hw (host values: they size the grid, nothing on the device is read by the host); 1..16384.
+ * dst == src is allowed (in place), otherwise the two must not overlap.  One launch: a 256-thread workgroup owns a 64 x 64 tile of one
+ * image, culls the image's rows against it in passes of ryolo_draw_rows_per_pass() = 256 rows into an LDS list and every pixel stops at
+ * the first (highest) row that covers it.  No workspace, no allocation, no atomics, one writer per byte, bytes of dst outside the images
+ * are not touched, capture-safe, bit-identical from run to run.  M == 0: with dst == src no launch, otherwise a copy of the images.
+ * RYOLO_EINVAL before any HIP call: a null src, dst, img_offset, img_hw or thick; n_img < 1 or above ryolo_draw_max_images() = 1024;
+ * M < 0; M > 0 with a null quad, det_off or color; quad not 16-byte aligned; a thick entry outside 1..255; max_h or max_w outside
+ * 1..16384; only some of the three label pointers.  The two queries need no device.  tests/draw_reference.py restates the definition. */
+int ryolo_draw_rows_per_pass(void);
+int ryolo_draw_max_images(void);
+int ryolo_draw_quads(const uint8_t *src, uint8_t *dst, const long long *img_offset, const int *img_hw /* [n_img][2] */, int n_img,
+                     int max_h, int max_w, const int *quad /* [M][8] */, const int *det_off /* [n_img+1] */, int M,
+                     const uint8_t *color /* [M][4] RGBx */, const int *thick /* host [n_img] */, const uint8_t *lab_bits,
+                     const long long *lab_off /* [M] */, const int *lab_rect /* [M][4]: x, y, w, h */, void *stream);
 
 
 /* Decode + score filter + compaction (no `io` tensor): the rows of ryolo_yolo_decode's `io` that the first half of

@@ -10,7 +10,10 @@
 //                     -- then order_points: stable sort by X (ties by corner index); the two left-most, stably by Y, are tl, bl; of the two
 //                     right-most the one farther from tl (squared distance) is br, on a tie the later one; the output row is
 //                     tl, tr, br, bl with every coordinate truncated toward zero to int32.
-// One thread per row, no workspace, no atomics.  tests/detect_reference.py restates both.
+// ryolo_det_corners   get_rotated_coors (utils/utils.py:702-725) per row: the same four turned corners in fp64, kept in THAT order
+//                     (corner 0 is where the drawn label is anchored, and order_points can return a sequence that is no cycle on ties)
+//                     and truncated toward zero to int32 -- the outline csrc/draw.hip draws.
+// One thread per row, no workspace, no atomics.  tests/detect_reference.py restates the first two, tests/draw_reference.py the third.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -72,6 +75,25 @@ __global__ __launch_bounds__(256) void det_quads_kernel(const float *__restrict_
     *(int4 *)(quad + (size_t)r * 8 + 4) = q1;
 }
 
+__global__ __launch_bounds__(256) void det_corners_kernel(const float *__restrict__ det, int M, int *__restrict__ quad) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= M) return;
+    const float4 v = *(const float4 *)(det + (size_t)r * 8);
+    const double cx = v.x, cy = v.y, w = v.z, h = v.w, a = det[(size_t)r * 8 + 4];
+    const double alpha = cos(-a), beta = sin(-a);
+    const double r02 = (1 - alpha) * cx - beta * cy, r12 = beta * cx + (1 - alpha) * cy;
+    const double tx[4] = {cx - w * 0.5, cx - w * 0.5, cx + w * 0.5, cx + w * 0.5};
+    const double ty[4] = {cy - h * 0.5, cy + h * 0.5, cy + h * 0.5, cy - h * 0.5};
+    int q[8];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {        // the corners stay in get_rotated_coors' order: no order_points
+        q[2 * k] = (int)(tx[k] * alpha + ty[k] * beta + r02);
+        q[2 * k + 1] = (int)(tx[k] * -beta + ty[k] * alpha + r12);
+    }
+    *(int4 *)(quad + (size_t)r * 8) = make_int4(q[0], q[1], q[2], q[3]);
+    *(int4 *)(quad + (size_t)r * 8 + 4) = make_int4(q[4], q[5], q[6], q[7]);
+}
+
 }  // namespace
 
 extern "C" {
@@ -89,6 +111,14 @@ int ryolo_det_quads(const float *det, int M, int *quad, void *stream) {
     if (M == 0) return RYOLO_OK;
     if (!det || !quad || ((uintptr_t)det & 15) || ((uintptr_t)quad & 15)) return RYOLO_EINVAL;
     hipLaunchKernelGGL(det_quads_kernel, dim3((M + 255) / 256), dim3(256), 0, (hipStream_t)stream, det, M, quad);
+    return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
+}
+
+int ryolo_det_corners(const float *det, int M, int *quad, void *stream) {
+    if (M < 0) return RYOLO_EINVAL;
+    if (M == 0) return RYOLO_OK;
+    if (!det || !quad || ((uintptr_t)det & 15) || ((uintptr_t)quad & 15)) return RYOLO_EINVAL;
+    hipLaunchKernelGGL(det_corners_kernel, dim3((M + 255) / 256), dim3(256), 0, (hipStream_t)stream, det, M, quad);
     return hipGetLastError() == hipSuccess ? RYOLO_OK : RYOLO_ELAUNCH;
 }
 

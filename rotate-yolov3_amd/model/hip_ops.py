@@ -343,6 +343,101 @@ def det_quads(det, out=None):
     return out
 
 
+def det_corners(det, out=None):
+    """get_rotated_coors of the reference for every row of det (fp32 [M, 8]) -> int32 [M, 8] rows (x, y of the corners (xmin, ymin),
+    (xmin, ymax), (xmax, ymax), (xmax, ymin) after the turn, in that order): the outlines draw_quads draws
+    (include/ryolo.h: ryolo_det_corners)."""
+    _check_det(det)
+    dev = det.device
+    if out is None:
+        out = torch.empty((det.shape[0], 8), dtype=torch.int32, device=dev)
+    elif not (torch.is_tensor(out) and out.dtype == torch.int32 and out.is_contiguous() and out.device == dev
+              and tuple(out.shape) == (det.shape[0], 8)):
+        raise RuntimeError("out must be a contiguous int32 [M, 8] tensor on det's device")
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().ryolo_det_corners(det.data_ptr(), det.shape[0], out.data_ptr(), _lib.stream_ptr(dev)), "ryolo_det_corners")
+    return out
+
+
+DRAW_ROWS_PER_PASS = 256      # rows a workgroup of csrc/draw.hip culls per pass (ryolo_draw_rows_per_pass(); a CPU test holds the two equal)
+DRAW_MAX_SIDE = 16384         # the largest image side ryolo_draw_quads accepts
+
+
+def draw_quads(cache_or_pixels, quad, det_off, color, thick, labels=None, out=None):
+    """One launch of csrc/draw.hip: the outlines quad[r] (int32 [M, 8], det_corners) and the label bitmaps painted over the pixels of an
+    image cache, the highest row on top (include/ryolo.h: ryolo_draw_quads).  Returns the drawn pixels, a uint8 tensor laid out like
+    cache.pixels; the cache itself is not written unless out is cache.pixels.
+    cache_or_pixels: a DeviceImageCache, or the tuple (pixels, img_offset, img_hw, hw) of its fields (hw: the HOST list of (h, w));
+    det_off: int32 [n_img + 1] row offsets per image; color: uint8 [M, 4] RGBx; thick: one int 1..255 or one per image, on the HOST;
+    labels: None or (lab_bits uint8 [nbytes], lab_off int64 [M], lab_rect int32 [M, 4] rows (x, y, w, h)) (utils.plots.pack_labels);
+    quad, det_off, color and labels on the pixels' device.  out: a uint8 tensor like pixels to draw into (pixels itself: in place)."""
+    import numpy as np
+    if isinstance(cache_or_pixels, (tuple, list)):
+        if len(cache_or_pixels) != 4:
+            raise RuntimeError("cache_or_pixels must be a DeviceImageCache or the tuple (pixels, img_offset, img_hw, hw)")
+        pixels, offs, hw, host_hw = cache_or_pixels
+    else:
+        pixels, offs, hw, host_hw = cache_or_pixels.pixels, cache_or_pixels.img_offset, cache_or_pixels.img_hw, cache_or_pixels.hw
+    if not (torch.is_tensor(pixels) and pixels.is_cuda and pixels.dtype == torch.uint8 and pixels.dim() == 1 and pixels.is_contiguous()):
+        raise RuntimeError("cache.pixels must be a contiguous uint8 [nbytes] GPU tensor")
+    dev = pixels.device
+    n_img = offs.numel() if torch.is_tensor(offs) else -1
+    if not (n_img >= 1 and offs.dtype == torch.int64 and offs.is_contiguous() and offs.device == dev and torch.is_tensor(hw)
+            and hw.dtype == torch.int32 and hw.is_contiguous() and hw.device == dev and tuple(hw.shape) == (n_img, 2)):
+        raise RuntimeError("cache.img_offset / cache.img_hw must be int64 [n] / int32 [n, 2] tensors on the cache's device")
+    host_hw = [(int(h), int(w)) for h, w in host_hw]
+    if len(host_hw) != n_img or min(min(s) for s in host_hw) < 1 or max(max(s) for s in host_hw) > DRAW_MAX_SIDE:
+        raise RuntimeError("cache.hw must hold the %d (h, w) of the images, every side in 1..%d" % (n_img, DRAW_MAX_SIDE))
+    if n_img > _lib.lib().ryolo_draw_max_images():
+        raise RuntimeError("cache holds %d images: draw_quads takes at most %d per call" % (n_img, _lib.lib().ryolo_draw_max_images()))
+    if not (torch.is_tensor(quad) and quad.dtype == torch.int32 and quad.dim() == 2 and quad.shape[1] == 8 and quad.is_contiguous()
+            and quad.device == dev):
+        raise RuntimeError("quad must be a contiguous int32 [M, 8] tensor on the pixels' device")
+    m = quad.shape[0]
+    if not (torch.is_tensor(det_off) and det_off.dtype == torch.int32 and det_off.dim() == 1 and det_off.numel() == n_img + 1
+            and det_off.is_contiguous() and det_off.device == dev):
+        raise RuntimeError("det_off must be a contiguous int32 [n_img + 1] tensor on the pixels' device (n_img = %d)" % n_img)
+    if not (torch.is_tensor(color) and color.dtype == torch.uint8 and color.is_contiguous() and color.device == dev
+            and tuple(color.shape) == (m, 4)):
+        raise RuntimeError("color must be a contiguous uint8 [M, 4] (RGBx) tensor on the pixels' device")
+    if torch.is_tensor(thick):
+        if thick.is_cuda or thick.is_floating_point():
+            raise RuntimeError("thick must be integers in host memory, not a %s tensor on %s" % (thick.dtype, thick.device))
+        thick = thick.numpy()
+    thick = np.asarray(thick)
+    if thick.ndim == 0:
+        thick = np.full(n_img, thick)
+    if not (thick.dtype.kind in 'iu' and thick.shape == (n_img,) and thick.min() >= 1 and thick.max() <= 255):
+        raise RuntimeError("thick must be one integer in 1..255 or one per image (%d), not %s %s" % (n_img, thick.dtype, thick.shape))
+    thick = np.ascontiguousarray(thick, dtype=np.int32)
+    bits_ptr = off_ptr = rect_ptr = None
+    if labels is not None:
+        if not (isinstance(labels, (tuple, list)) and len(labels) == 3 and all(torch.is_tensor(t) for t in labels)):
+            raise RuntimeError("labels must be None or the tuple (lab_bits, lab_off, lab_rect) of tensors")
+        bits, loff, rect = labels
+        if not (bits.dtype == torch.uint8 and bits.dim() == 1 and bits.is_contiguous() and bits.device == dev):
+            raise RuntimeError("labels: lab_bits must be a contiguous uint8 [nbytes] tensor on the pixels' device")
+        if not (loff.dtype == torch.int64 and loff.is_contiguous() and loff.device == dev and tuple(loff.shape) == (m,)):
+            raise RuntimeError("labels: lab_off must be a contiguous int64 [M] tensor on the pixels' device")
+        if not (rect.dtype == torch.int32 and rect.is_contiguous() and rect.device == dev and tuple(rect.shape) == (m, 4)):
+            raise RuntimeError("labels: lab_rect must be a contiguous int32 [M, 4] tensor on the pixels' device")
+        # every rectangle must lie inside lab_bits (lab_off[r] + lw * lh <= nbytes: the caller's duty, pack_labels keeps it), so
+        # without a single label byte every lw * lh is 0 and the call is the one without labels
+        if m and bits.numel():
+            bits_ptr, off_ptr, rect_ptr = bits.data_ptr(), loff.data_ptr(), rect.data_ptr()
+    if out is None:
+        out = torch.empty_like(pixels)
+    elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.is_contiguous() and out.device == dev
+              and tuple(out.shape) == tuple(pixels.shape)):
+        raise RuntimeError("out must be a contiguous uint8 tensor of the shape of the pixels, on their device")
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().ryolo_draw_quads(pixels.data_ptr(), out.data_ptr(), offs.data_ptr(), hw.data_ptr(), n_img,
+                                               max(h for h, _ in host_hw), max(w for _, w in host_hw), quad.data_ptr() if m else None,
+                                               det_off.data_ptr(), m, color.data_ptr() if m else None, thick.ctypes.data, bits_ptr, off_ptr,
+                                               rect_ptr, _lib.stream_ptr(dev)), "ryolo_draw_quads")
+    return out
+
+
 def nhwc_bf16_to_nchw_f32(x):
     cs = _check_nhwc(x, "x")
     n, h, w, c = x.shape

@@ -9,7 +9,8 @@ Changed: data parallelism is ONE PROCESS PER GPU (launch with `python -m torch.d
 train.py ...`) with bucketed RCCL all-reduce overlapped with backward (rotate-yolov3_amd/dist.py) instead of the
 reference's broken single-process DDP; the input pipeline is synthetic (`--synthetic N` images per epoch) unless `--real-data`
 reads the `train` / `valid` image lists of `--data` through the device loader (utils/datasets.py: images cached on the GPU, letterbox
-and augmentation in one HIP launch per batch, csrc/augment.hip).  On a GPU the training-mode forward AND backward run the hand-written HIP
+and augmentation in one HIP launch per batch, csrc/augment.hip); `--plot-batch` writes the first batch with its targets drawn in
+(train_batch0.jpg, as the reference does: utils/plots.py over csrc/draw.hip).  On a GPU the training-mode forward AND backward run the hand-written HIP
 TrainEngine (conv forward / dgrad / wgrad on MFMA, BatchNorm + PReLU kernels, fused loss, one-launch SGD or Adam;
 rotate-yolov3_amd/model/train_engine.py); CPU tensors and `--backend torch` (model.backend = 'torch') take the ATen operator chain --
 the way to train a "matrix" cfg (weight_from / d-convolutional layers), which the TrainEngine refuses; `--shared-conv hip` then runs
@@ -87,6 +88,21 @@ def set_epoch_lr(optimizer, hyp, epoch, epochs):
     for g in optimizer.param_groups:
         g['lr'] = g['initial_lr'] * f
     return f
+
+
+def plot_first_batch(imgs, targets, fname):
+    """--plot-batch: the reference's train_batch0.jpg (train.py:248-251) -- the batch as the model gets it, with its targets drawn in
+    (utils/plots.py over csrc/draw.hip): the way to see whether the device augmentation and the host's label arithmetic agree"""
+    from rotate_yolov3_amd.model import hip_ops
+    from rotate_yolov3_amd.model.nhwc_batch import NHWC8Batch
+    from rotate_yolov3_amd.utils.plots import plot_images
+    if not imgs.is_cuda:
+        print('NOTE: --plot-batch draws on the device (ryolo_draw_quads); the batch is on %s: no %s' % (imgs.device, fname))
+        return
+    if not isinstance(imgs, NHWC8Batch):                 # the synthetic loader's fp32 NCHW tensor
+        imgs = NHWC8Batch(hip_ops.nchw_f32_to_nhwc_bf16(imgs))
+    plot_images(imgs, targets, fname)
+    print('--plot-batch: wrote %s' % fname)
 
 
 def train(opt, hyp):
@@ -168,6 +184,8 @@ def train(opt, hyp):
         s = ''
         for i, (imgs, targets, _, _) in enumerate(loader):
             ni = i + nb * epoch
+            if i == 0 and epoch == start_epoch and rank == 0 and getattr(opt, 'plot_batch', False):
+                plot_first_batch(imgs, targets, 'train_batch0.jpg')
             do_step = ni % opt.accumulate == 0
             dp.sync = do_step                 # micro-batches that do not step only accumulate locally (no collective)
             pred = model(imgs)
@@ -245,6 +263,8 @@ def make_parser():
     parser.add_argument('--real-data', action='store_true',
                         help="train on the `train` image list of --data (evaluate on its `valid` list) through the device loader "
                              "instead of synthetic images; needs a GPU and Pillow")
+    parser.add_argument('--plot-batch', action='store_true',
+                        help="write train_batch0.jpg: the first batch of the first epoch with its targets drawn in (rank 0; needs a GPU and Pillow)")
     parser.add_argument('--bucket-mb', type=float, default=64.0, help='gradient all-reduce bucket size')
     parser.add_argument('--eager-loss', action='store_true', help='eager compute_loss mirror instead of the graph-captured loss')
     parser.add_argument('--backend', choices=['hip', 'torch'], default='hip',

@@ -21,6 +21,8 @@ load cfg (+ .pt / darknet .weights), forward on the HIP engine, rotated NMS, wri
   * the exception to "anything that does not exist": a camera number (`0`), a stream URL (rtsp:// rtmp:// http:// https://) or a video
     file that exists.  The reference opens these with OpenCV; here they are refused with a clear error instead of falling back to
     synthetic images.
+--nms-style MERGE (all three kinds of source; default OR, the greedy NMS): every kept box becomes the score-weighted mean of the boxes it
+suppresses (utils/nms/nms.py).  With several sizes that happens in the merge over the scales, where one object gives one estimate per size.
 The outline is this port's own exact definition (include/ryolo.h: ryolo_draw_quads), not cv2.polylines pixel for pixel; the label is
 upright.  Displaying the pictures (--view-img) and video output are out of scope."""
 import argparse
@@ -131,7 +133,8 @@ def detect_image_files(model, opt, device):
     icdar_files = []
     for paths, cache, shapes in dataset:
         n = len(paths)
-        out, det, det_off = detect_images(model, cache, n, shapes, sizes, opt.conf_thres, opt.nms_thres, slots=opt.batch_size)
+        out, det, det_off = detect_images(model, cache, n, shapes, sizes, opt.conf_thres, opt.nms_thres, slots=opt.batch_size,
+                                          nms_style=getattr(opt, 'nms_style', 'OR'))
         quads = hip_ops.det_quads(det).cpu().tolist() if icdar else None
         off = det_off.cpu().tolist()
         rows = det.cpu().tolist()
@@ -170,6 +173,8 @@ def detect_image_files(model, opt, device):
 def detect(opt):
     if getattr(opt, 'save_img', False) and is_image_source(opt.source):
         check_save_img_output(opt)       # before anything is loaded or written
+    from rotate_yolov3_amd.utils.nms.nms import check_nms_style
+    check_nms_style(getattr(opt, 'nms_style', 'OR'))
     device = getattr(opt, 'torch_device', None) or torch.device('cuda:0')
     hyp = hyp_parse(opt.hyp) if opt.hyp and os.path.isfile(opt.hyp) else {'context_factor': 1.0}
     model = Darknet(opt.cfg, hyp)
@@ -201,10 +206,11 @@ def detect(opt):
     os.makedirs(opt.output, exist_ok=True)
     t0 = time.time()
     n_det = 0
+    style = {} if getattr(opt, 'nms_style', 'OR') == 'OR' else {'nms_style': opt.nms_style}
     with torch.no_grad():
         for b in range(0, len(imgs), opt.batch_size):
             # forward + non_max_suppression(pred, conf, nms) of the reference (detect.py:91-99), fused on the GPU
-            for i, det in enumerate(model.detect(imgs[b:b + opt.batch_size].to(device), opt.conf_thres, opt.nms_thres)):
+            for i, det in enumerate(model.detect(imgs[b:b + opt.batch_size].to(device), opt.conf_thres, opt.nms_thres, **style)):
                 with open(os.path.join(opt.output, 'img_%d.txt' % (b + i)), 'w') as f:
                     if det is not None:
                         n_det += len(det)
@@ -213,8 +219,9 @@ def detect(opt):
     print('Done. %d images, %d detections (%.3fs)' % (len(imgs), n_det, time.time() - t0))
 
 
-if __name__ == '__main__':
-    from rotate_yolov3_amd.utils.cli import add_ignored, pick_device, report_ignored
+def build_parser():
+    """-> (parser, names of the flags that are accepted and ignored)"""
+    from rotate_yolov3_amd.utils.cli import add_ignored
     parser = argparse.ArgumentParser()                                   # the reference's flags (detect.py:280-295), same defaults
     parser.add_argument('--hyp', type=str, default='cfg/ICDAR/hyp.py', help='hyper-parameter path')
     parser.add_argument('--cfg', type=str, default='cfg/ICDAR/yolov3_608_dh_o8_ga.cfg', help='cfg file path')
@@ -233,11 +240,18 @@ if __name__ == '__main__':
     parser.add_argument('--icdar', action='store_true', help='also write <output>/icdar/res_<stem>.txt and <output>/icdar_result.zip')
     parser.add_argument('--save-img', action='store_true', help='image files only: also write <output>/<image name>, the picture with the boxes and labels drawn in (on the device)')
     parser.add_argument('--line-thickness', type=int, default=0, help='outline thickness of --save-img in pixels, 1..255 (0: round(0.002 (h + w) / 2) + 1 per image)')
+    parser.add_argument('--nms-style', type=str, default='OR', choices=['OR', 'MERGE'], help='OR: greedy rotated NMS; MERGE: every kept box becomes the score-weighted mean of the boxes it suppresses (with several scales: in the merge over the scales)')
     ignored = add_ignored(parser, [
         ('--data', dict(type=str, default='data/tiny.data', help='*.data file path: with --save-img its `names` file names the classes in the labels')),
         ('--fourcc', dict(type=str, default='mp4v', help='output video codec')),
         ('--half', dict(action='store_true', help='half precision FP16 inference (the HIP engine always computes in bf16 with fp32 accumulation)')),
         ('--view-img', dict(action='store_true', help='display results'))])
+    return parser, ignored
+
+
+if __name__ == '__main__':
+    from rotate_yolov3_amd.utils.cli import pick_device, report_ignored
+    parser, ignored = build_parser()
     opt = parser.parse_args()
     print(opt)
     report_ignored(parser, opt, [n for n in ignored if not (n == 'data' and opt.save_img)])     # --save-img reads --data

@@ -85,6 +85,32 @@ int ryolo_rnms_segmented(const float *dets, int m, int row_stride, const int32_t
                          int max_seg_len, float thr, unsigned char *keep_flags, void *workspace, size_t workspace_bytes,
                          void *stream);
 
+/* Weighted-merge rotated NMS -- the `nms_style == 'MERGE'` branch of the reference (utils/nms/nms.py:115-127): the kept box becomes the
+ * score-weighted mean of the boxes it suppresses.  Input as ryolo_rnms_segmented; three outputs of m rows each (rows outside every
+ * segment are left untouched in all three):
+ *   keep_flags [m] uint8   bit-identical to what ryolo_rnms_segmented writes for the same input (the same kernels, tiles and scan).
+ *   owner      [m] int32   kept row j: owner[j] = j.  Suppressed row j: the global row index of the smallest i < j of j's segment with
+ *                          keep[i] and devRotateIoU(box_i, box_j) > thr -- the same fp32 value, box_i as first argument, and the same
+ *                          strict comparison as the mask kernel's (above).  That is the reference's loop: a box belongs to the first kept
+ *                          box at whose turn it is still alive and overlaps it.  The kept box is always a member of its own group (the
+ *                          reference relies on IoU(b, b) > thr for that; this definition does not).
+ *   merged     [m, 5] fp32 kept row i with members M(i) = { j : owner[j] = i } and weights w_j = score_j:
+ *                          merged[i][f] = (sum_j w_j * v_j[f]) / (sum_j w_j) for f in cx, cy, w, h, a.  Products, sums and the one
+ *                          division per field in fp64, the quotient rounded once to fp32.  The order of the sums is fixed by the members'
+ *                          positions in their segment (no floating-point atomics): two calls on the same input give the same bits.  Rows that are not kept:
+ *                          five zeros.  sum_j w_j not a finite number greater than 0: the kept row's own five fields.
+ * Angles (the one deviation from the reference, which takes the plain mean): a box is unchanged by a -> a +- pi, so a member's angle
+ * enters the sum as a_j - pi * rint((a_j - a_i) / pi), a_i the owner's angle, in fp64 with pi = 3.14159265358979323846 and rint to nearest
+ * even: within pi/2 of a_i.  The merged angle is not wrapped back.  When every member is within pi/2 of its owner this is the reference's
+ * arithmetic.  Score, class confidence and class are not this call's business; which rows survive is exactly what the plain call decides.
+ * No polygon IoU is evaluated a second time: the owner comes from the tiles and summaries the mask kernel left in the workspace.  The call
+ * is a linear chain of launches on `stream` (extent, corners, mask, scan, keep words, owner, merge, and two small memsets): no second
+ * stream, no host synchronisation, no host read; capturable.  Arguments and return codes as ryolo_rnms_segmented; a NULL owner or merged is RYOLO_EINVAL. */
+size_t ryolo_rnms_merge_segmented_workspace_bytes(int m, int num_segments, int max_seg_len);
+int ryolo_rnms_merge_segmented(const float *dets, int m, int row_stride, const int32_t *seg_offsets, int num_segments,
+                               int max_seg_len, float thr, unsigned char *keep_flags, int32_t *owner, float *merged /* [m,5] */,
+                               void *workspace, size_t workspace_bytes, void *stream);
+
 /* Measurement hook (bench.py's nms.roofline): while `device_counter` is non-NULL every subsequent ryolo_rnms /
  * ryolo_rnms_segmented call adds the number of box pairs whose exact polygon IoU it evaluated (pairs that survive the
  * bounding-circle reject) to *device_counter (uint64, zeroed by the caller).  NULL switches it off.  Not thread safe. */

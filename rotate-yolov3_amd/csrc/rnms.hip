@@ -962,6 +962,241 @@ static SidePool *side_pool() {
 }
 constexpr int SPLIT_MIN_ROWS = 320;      // block rows (n > 20 416) from which the split pays (16 384 boxes: 0.495 vs 0.477 ms; 24 000: 0.750 vs 0.791)
 
+// ------------------------------------------------------------------------------------------------ weighted merge (MERGE style)
+// ryolo_rnms_merge_segmented (definition: include/ryolo.h) = the segmented call + three short passes over what it left in its workspace.
+// No IoU is evaluated here: which kept box suppresses a discarded one is already in the mask kernel's summaries and word tiles.
+//   M0  keepwords  one wave per block row of a segment: its 64 keep flags as one word (ballot)
+//   M1  owner      one workgroup of OWNER_WAVES waves per block COLUMN cb of a segment, lane c = box cb*64 + c.  The owner is a minimum
+//                  -- the lowest kept row with a bit in the column -- so the block rows 0 .. cb are dealt out to the waves (block row
+//                  mod OWNER_WAVES) and the waves' candidates meet in LDS.  A wave takes its block rows in ascending order, 64 summaries
+//                  and keep words fetched per round (lane l: block row base + l); empty tiles and tiles of a block row without a kept
+//                  box are never visited.  Listed tile: the pairs of the lane's column against the keep word; dense tile: column word &
+//                  keep word, lowest bit.  A lane's first hit is its candidate; a wave stops when no lane of it is still looking.
+//                  Wave 0 then writes the owners and marks, in a byte per tile (zeroed before), the tiles in which a box of this column
+//                  block found its owner: at most one tile per suppressed box.
+//   M2  merge      one workgroup of GATHER_WAVES waves per block ROW rb of a segment, lane r = kept box rb*64 + r with six fp64
+//                  accumulators (sum of w, sums of w * field).  The marked tiles of the block row are dealt out to the waves (tile mod
+//                  GATHER_WAVES); a wave walks its tiles left to right, GATHER_BATCH at a time (their owners, then their members' rows,
+//                  as independent loads); the members of a tile (owner inside this block row) are taken one at a time in ascending column
+//                  order, their row broadcast with v_readlane and added by the owning lane alone.  The waves' partial sums meet in LDS and
+//                  wave 0 adds them, after the box itself, in wave order: the order of every sum is a function of the members' positions
+//                  in the segment alone.  No atomics.
+// (The first form -- one wave per column block walking all its block rows, one wave per block row visiting every non-empty tile -- cost
+//  1.05 ms on top of the 2.94-ms plain call on 50 000 boxes; with the owner pass split and the marks, 0.84 ms, 0.63 of them the merge pass:
+//  the first block rows own most of the boxes, and one wave followed up to 782 dependent loads.  profiles/nms_merge.txt: this form.)
+__device__ __forceinline__ unsigned long long readlane64(unsigned long long v, int l) {
+    return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (unsigned)__builtin_amdgcn_readlane((int)v, l);
+}
+__device__ __forceinline__ float readlanef(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+
+constexpr int MERGE_WAVES = 4;            // waves per workgroup of the keep-word and merge passes (independent: no LDS, no barrier)
+
+__global__ void __launch_bounds__(MERGE_WAVES *WAVE)
+rnms_keepwords_kernel(const unsigned char *__restrict__ flags, const int32_t *__restrict__ seg_off, int Wmax,
+                      unsigned long long *__restrict__ keepw) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int s = blockIdx.y, lo = seg_off[s], n = seg_off[s + 1] - lo;
+    const int rb = blockIdx.x * MERGE_WAVES + (threadIdx.x >> 6);
+    if (rb >= Wmax) return;                                        // (wave-uniform)
+    const int i = rb * WAVE + lane;
+    const unsigned long long w = __ballot(i < n && flags[lo + i] != 0);     // block rows past the segment's end: 0
+    if (lane == 0) keepw[(size_t)s * Wmax + rb] = w;
+}
+
+constexpr int OWNER_WAVES = 8;            // waves per column block of the owner pass (a power of two, at most 64)
+constexpr int NO_OWNER = 0x7fffffff;
+
+__global__ void __launch_bounds__(OWNER_WAVES *WAVE)
+rnms_owner_kernel(const unsigned long long *__restrict__ tiles, const uint4 *__restrict__ summ, const unsigned long long *__restrict__ keepw,
+                  const int32_t *__restrict__ seg_off, long long seg_tile_stride, int Wmax, int32_t *__restrict__ owner,
+                  unsigned char *__restrict__ has_member) {
+    __shared__ int cand[OWNER_WAVES][WAVE];
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wv = threadIdx.x >> 6;
+    const int s = blockIdx.y, lo = seg_off[s], n = seg_off[s + 1] - lo;
+    const int W = (n + WAVE - 1) / WAVE;
+    const int cb = blockIdx.x;
+    if (n <= 0 || cb >= W || cb >= Wmax) return;                   // (workgroup-uniform)
+    tiles += (size_t)s * seg_tile_stride * WAVE;
+    summ += (size_t)s * seg_tile_stride;
+    has_member += (size_t)s * seg_tile_stride;
+    keepw += (size_t)s * Wmax;
+    const int j = cb * WAVE + lane;
+    const bool valid = j < n;
+    const bool kept = (keepw[cb] >> lane) & 1ull;                  // (bits past the segment's end are 0)
+    int own = NO_OWNER;
+    bool need = valid && !kept;
+    // this wave's block rows: rb mod OWNER_WAVES == wv (64 is a multiple of OWNER_WAVES: the same lanes of every round)
+    unsigned long long stripe = 0ull;
+#pragma unroll
+    for (int l = 0; l < WAVE; l += OWNER_WAVES) stripe |= 1ull << l;
+    stripe <<= wv;
+    for (int base = 0; base <= cb && __ballot(need); base += WAVE) {
+        const int rbl = base + lane;
+        uint4 s4 = make_uint4(0u, 0u, 0u, 0u);
+        unsigned long long kw = 0ull;
+        if (rbl <= cb && ((stripe >> lane) & 1ull)) {
+            s4 = summ[tile_base(rbl, W) + (cb - rbl)];
+            kw = keepw[rbl];
+        }
+        unsigned long long todo = __ballot((s4.x & 0xffffu) != 0u && kw != 0ull);
+        while (todo && __ballot(need)) {                           // (wave-uniform)
+            const int l = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const int rb = base + l;
+            const unsigned long long kwl = readlane64(kw, l);
+            uint4 t4;
+            t4.x = (unsigned)__builtin_amdgcn_readlane((int)s4.x, l);
+            t4.y = (unsigned)__builtin_amdgcn_readlane((int)s4.y, l);
+            t4.z = (unsigned)__builtin_amdgcn_readlane((int)s4.z, l);
+            t4.w = (unsigned)__builtin_amdgcn_readlane((int)s4.w, l);
+            const unsigned cnt = t4.x & 0xffffu;
+            unsigned long long hit = 0ull;                         // kept rows of this tile that suppress the lane's column
+            if (cnt == SUMM_DENSE) {
+                hit = tiles[(tile_base(rb, W) + (cb - rb)) * WAVE + lane] & kwl;       // (a dense tile stores all 64 column words)
+            } else {
+                for (unsigned k = 1; k <= cnt; k++) {
+                    const unsigned e = summ_entry(t4, (int)k);
+                    if ((int)(e & 63u) == lane) hit |= 1ull << (e >> 6);
+                }
+                hit &= kwl;
+            }
+            if (need && hit) {
+                own = rb * WAVE + __builtin_ctzll(hit);
+                need = false;
+            }
+        }
+    }
+    cand[wv][lane] = own;
+    __syncthreads();
+    if (wv != 0) return;
+#pragma unroll
+    for (int w = 1; w < OWNER_WAVES; w++) own = min(own, cand[w][lane]);
+    // (a suppressed box always finds its owner: the scan removed it because of one of these bits; it would own itself otherwise)
+    const bool found = valid && !kept && own != NO_OWNER;
+    if (!found) own = j;
+    if (valid) owner[lo + j] = lo + own;
+    // one mark per block row that owns a box of this column block
+    const int orb = own >> 6;
+    unsigned long long m = __ballot(found);
+    while (m) {                                                    // (wave-uniform)
+        const int rb = __builtin_amdgcn_readlane(orb, __builtin_ctzll(m));
+        if (lane == 0) has_member[tile_base(rb, W) + (cb - rb)] = 1;
+        m &= ~__ballot(orb == rb);
+    }
+}
+
+constexpr int GATHER_WAVES = 8;           // waves per block row of the merge pass (a power of two, at most 64)
+constexpr int GATHER_BATCH = 4;           // marked tiles whose owners and member rows are fetched together (two dependent loads per tile)
+
+__global__ void __launch_bounds__(GATHER_WAVES *WAVE)
+rnms_merge_kernel(const float *__restrict__ dets, int row_stride, const unsigned char *__restrict__ has_member, const unsigned long long *__restrict__ keepw,
+                  const int32_t *__restrict__ owner, const int32_t *__restrict__ seg_off, long long seg_tile_stride, int Wmax,
+                  float *__restrict__ merged) {
+    __shared__ double part[GATHER_WAVES][6][WAVE];
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wv = threadIdx.x >> 6;
+    const int s = blockIdx.y, lo = seg_off[s], n = seg_off[s + 1] - lo;
+    const int W = (n + WAVE - 1) / WAVE;
+    const int rb = blockIdx.x;
+    if (n <= 0 || rb >= W || rb >= Wmax) return;                   // (workgroup-uniform)
+    has_member += (size_t)s * seg_tile_stride + tile_base(rb, W);       // the tiles of block row rb: columns rb .. W-1, back to back
+    const unsigned long long keepword = keepw[(size_t)s * Wmax + rb];
+    const int i = rb * WAVE + lane;
+    const bool valid = i < n;
+    const bool kept = (keepword >> lane) & 1ull;
+    float own[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (kept) {
+        const float *r = dets + (size_t)(lo + i) * row_stride;
+#pragma unroll
+        for (int f = 0; f < 6; f++) own[f] = r[f];
+    }
+    const double PI = 3.14159265358979323846;
+    const double ai = (double)own[4];
+    // this wave's share of the block row: the tiles with (column block - rb) mod GATHER_WAVES == wv, in ascending order
+    double sw = 0.0, acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (keepword) {                                                // (workgroup-uniform; no kept box in this block row: nothing to gather)
+        unsigned long long stripe = 0ull;
+#pragma unroll
+        for (int l = 0; l < WAVE; l += GATHER_WAVES) stripe |= 1ull << l;
+        stripe <<= wv;
+        const int ntile = W - rb;
+        for (int base = 0; base < ntile; base += WAVE) {
+            unsigned char mark = 0;
+            if (base + lane < ntile) mark = has_member[base + lane];
+            unsigned long long todo = __ballot(mark != 0) & stripe;
+            while (todo) {                                         // (wave-uniform)
+                int o[GATHER_BATCH], jj[GATHER_BATCH];
+                float v[GATHER_BATCH][6];
+                unsigned long long mm[GATHER_BATCH];
+#pragma unroll
+                for (int b = 0; b < GATHER_BATCH; b++) {           // the owners of up to GATHER_BATCH marked tiles: independent loads
+                    o[b] = -1;
+                    jj[b] = 0;
+                    if (todo) {
+                        jj[b] = (rb + base + __builtin_ctzll(todo)) * WAVE + lane;             // the lane's column box of this tile
+                        todo &= todo - 1;
+                        if (jj[b] < n) o[b] = owner[lo + jj[b]] - lo;
+                        if (o[b] == jj[b]) o[b] = -1;              // a kept box: in its own group, added by wave 0 below
+                    }
+                }
+#pragma unroll
+                for (int b = 0; b < GATHER_BATCH; b++) {           // the rows of their members: independent loads again
+                    const bool member = o[b] >= rb * WAVE && o[b] < rb * WAVE + WAVE;          // suppressed, by a box of this block row
+#pragma unroll
+                    for (int f = 0; f < 6; f++) v[b][f] = 0.f;
+                    if (member) {
+                        const float *r = dets + (size_t)(lo + jj[b]) * row_stride;
+#pragma unroll
+                        for (int f = 0; f < 6; f++) v[b][f] = r[f];
+                    }
+                    mm[b] = __ballot(member);
+                }
+#pragma unroll
+                for (int b = 0; b < GATHER_BATCH; b++) {
+                    while (mm[b]) {                                // ascending column inside ascending tiles: a fixed summation order
+                        const int c = __builtin_ctzll(mm[b]);
+                        mm[b] &= mm[b] - 1;
+                        const int r = __builtin_amdgcn_readlane(o[b], c) - rb * WAVE;
+                        float m[6];
+#pragma unroll
+                        for (int f = 0; f < 6; f++) m[f] = readlanef(v[b][f], c);
+                        if (lane == r) {
+                            const double w = (double)m[5];
+                            const double a = (double)m[4] - PI * rint(((double)m[4] - ai) / PI);
+                            sw = sw + w;
+#pragma unroll
+                            for (int f = 0; f < 4; f++) acc[f] = acc[f] + w * (double)m[f];
+                            acc[4] = acc[4] + w * a;
+                        }
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int f = 0; f < 5; f++) part[wv][f][lane] = acc[f];
+    part[wv][5][lane] = sw;
+    __syncthreads();
+    if (wv != 0 || !valid) return;
+    // the box itself, then the waves' partial sums in wave order
+    sw = (double)own[5];
+#pragma unroll
+    for (int f = 0; f < 5; f++) acc[f] = (double)own[5] * (double)own[f];
+    for (int w = 0; w < GATHER_WAVES; w++) {
+#pragma unroll
+        for (int f = 0; f < 5; f++) acc[f] = acc[f] + part[w][f][lane];
+        sw = sw + part[w][5][lane];
+    }
+    float out[5];
+    const bool ok = sw > 0.0 && sw <= 1.7976931348623157e308;      // a finite number greater than 0 (NaN compares false)
+#pragma unroll
+    for (int f = 0; f < 5; f++) out[f] = kept ? (ok ? (float)(acc[f] / sw) : own[f]) : 0.f;
+    float *dst = merged + (size_t)(lo + i) * 5;
+#pragma unroll
+    for (int f = 0; f < 5; f++) dst[f] = out[f];
+}
+
 }  // namespace
 
 extern "C" {
@@ -1089,15 +1324,11 @@ size_t ryolo_rnms_segmented_workspace_bytes(int m, int num_segments, int max_seg
            align256(8 * sizeof(uint32_t));
 }
 
-int ryolo_rnms_segmented(const float *dets, int m, int row_stride, const int32_t *seg_offsets, int num_segments,
-                         int max_seg_len, float thr, unsigned char *keep_flags, void *workspace, size_t workspace_bytes,
-                         void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (m < 0 || num_segments < 0) return RYOLO_EINVAL;
-    if (m == 0 || num_segments == 0) return RYOLO_OK;
-    if (!dets || !seg_offsets || !keep_flags || !workspace || row_stride < 6 || max_seg_len <= 0) return RYOLO_EINVAL;
-    if (max_seg_len > RYOLO_RNMS_MAX_BOXES) return RYOLO_ETOOBIG;
-    if (workspace_bytes < ryolo_rnms_segmented_workspace_bytes(m, num_segments, max_seg_len)) return RYOLO_EINVAL;
+// extent -> corners -> mask -> scan of a segmented call (arguments checked by the caller); *summ_out / *tiles_out: where the mask kernel's
+// summaries and word tiles lie in the workspace, for the merge passes that follow
+static int rnms_segmented_enqueue(const float *dets, int m, int row_stride, const int32_t *seg_offsets, int num_segments, int max_seg_len,
+                                  float thr, unsigned char *keep_flags, void *workspace, hipStream_t stream, uint4 **summ_out,
+                                  unsigned long long **tiles_out) {
     const long long nt1 = seg_tiles(max_seg_len);
     char *ws = (char *)workspace;
     float4 *P0 = (float4 *)ws; ws += align256(sizeof(float4) * (size_t)m);
@@ -1118,6 +1349,61 @@ int ryolo_rnms_segmented(const float *dets, int m, int row_stride, const int32_t
     hipLaunchKernelGGL(rnms_scan_kernel, dim3((unsigned)num_segments), dim3(SCAN_THREADS), smem, stream, 0, tiles, summ,
                        (const int32_t *)nullptr, keep_flags, (int64_t *)nullptr, (int32_t *)nullptr, seg_offsets, nt1, 0, -1,
                        (unsigned long long *)nullptr);
+    *summ_out = summ;
+    *tiles_out = tiles;
+    return check_launch();
+}
+
+int ryolo_rnms_segmented(const float *dets, int m, int row_stride, const int32_t *seg_offsets, int num_segments,
+                         int max_seg_len, float thr, unsigned char *keep_flags, void *workspace, size_t workspace_bytes,
+                         void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (m < 0 || num_segments < 0) return RYOLO_EINVAL;
+    if (m == 0 || num_segments == 0) return RYOLO_OK;
+    if (!dets || !seg_offsets || !keep_flags || !workspace || row_stride < 6 || max_seg_len <= 0) return RYOLO_EINVAL;
+    if (max_seg_len > RYOLO_RNMS_MAX_BOXES) return RYOLO_ETOOBIG;
+    if (workspace_bytes < ryolo_rnms_segmented_workspace_bytes(m, num_segments, max_seg_len)) return RYOLO_EINVAL;
+    uint4 *summ;
+    unsigned long long *tiles;
+    return rnms_segmented_enqueue(dets, m, row_stride, seg_offsets, num_segments, max_seg_len, thr, keep_flags, workspace, stream, &summ,
+                                  &tiles);
+}
+
+// ---- weighted merge: the segmented call, then keep words -> owner -> merge (kernels M0 - M2 above); the keep words (one per block row
+// and segment) and the owner pass's tile marks (a byte per tile) lie behind the segmented call's workspace
+size_t ryolo_rnms_merge_segmented_workspace_bytes(int m, int num_segments, int max_seg_len) {
+    const size_t base = ryolo_rnms_segmented_workspace_bytes(m, num_segments, max_seg_len);
+    if (base == 0) return 0;
+    const size_t W = ((size_t)max_seg_len + WAVE - 1) / WAVE;
+    return base + align256(sizeof(unsigned long long) * W * (size_t)num_segments) + align256((size_t)seg_tiles(max_seg_len) * (size_t)num_segments);
+}
+
+int ryolo_rnms_merge_segmented(const float *dets, int m, int row_stride, const int32_t *seg_offsets, int num_segments, int max_seg_len,
+                               float thr, unsigned char *keep_flags, int32_t *owner, float *merged, void *workspace,
+                               size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (m < 0 || num_segments < 0) return RYOLO_EINVAL;
+    if (m == 0 || num_segments == 0) return RYOLO_OK;
+    if (!dets || !seg_offsets || !keep_flags || !owner || !merged || !workspace || row_stride < 6 || max_seg_len <= 0) return RYOLO_EINVAL;
+    if (max_seg_len > RYOLO_RNMS_MAX_BOXES) return RYOLO_ETOOBIG;
+    if (workspace_bytes < ryolo_rnms_merge_segmented_workspace_bytes(m, num_segments, max_seg_len)) return RYOLO_EINVAL;
+    uint4 *summ;
+    unsigned long long *tiles;
+    const int rc = rnms_segmented_enqueue(dets, m, row_stride, seg_offsets, num_segments, max_seg_len, thr, keep_flags, workspace, stream,
+                                          &summ, &tiles);
+    if (rc != RYOLO_OK) return rc;
+    unsigned long long *keepw =
+        (unsigned long long *)((char *)workspace + ryolo_rnms_segmented_workspace_bytes(m, num_segments, max_seg_len));
+    const int W = (max_seg_len + WAVE - 1) / WAVE;
+    const long long nt1 = seg_tiles(max_seg_len);
+    unsigned char *has_member = (unsigned char *)keepw + align256(sizeof(unsigned long long) * (size_t)W * (size_t)num_segments);
+    if (hipMemsetAsync(has_member, 0, (size_t)nt1 * (size_t)num_segments, stream) != hipSuccess) return RYOLO_ELAUNCH;
+    const dim3 grid((unsigned)((W + MERGE_WAVES - 1) / MERGE_WAVES), (unsigned)num_segments), block(MERGE_WAVES * WAVE);
+    hipLaunchKernelGGL(rnms_keepwords_kernel, grid, block, 0, stream, keep_flags, seg_offsets, W, keepw);
+    hipLaunchKernelGGL(rnms_owner_kernel, dim3((unsigned)W, (unsigned)num_segments), dim3(OWNER_WAVES * WAVE), 0, stream, tiles, summ, keepw,
+                       seg_offsets, nt1, W, owner, has_member);
+    hipLaunchKernelGGL(rnms_merge_kernel, dim3((unsigned)W, (unsigned)num_segments), dim3(GATHER_WAVES * WAVE), 0, stream, dets, row_stride,
+                       has_member, keepw, owner, seg_offsets, nt1, W, merged);
     return check_launch();
 }
 

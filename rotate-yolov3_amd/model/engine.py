@@ -337,12 +337,14 @@ class HipEngine(object):
         self._launch_input(x)
         self._launch_layers()
 
-    def detect(self, x, conf_thres=0.5, nms_thres=0.5, capacity=1 << 18):
+    def detect(self, x, conf_thres=0.5, nms_thres=0.5, capacity=1 << 18, nms_style='OR'):
         """forward + post-processing for inference: the yolo layers run the fused decode + confidence filter +
         compaction kernel (ryolo_yolo_decode_filter; the [bs, rows, no] `io` tensor is never written), the survivors go
         through ONE segmented rotated-NMS launch.  Returns what non_max_suppression(model(x)[0], conf_thres, nms_thres)
-        returns: list[bs] of [k, 8] rows (x, y, w, h, a, score, class_conf, class) by descending score, or None."""
-        from ..utils.nms.nms import nms_from_candidates
+        returns: list[bs] of [k, 8] rows (x, y, w, h, a, score, class_conf, class) by descending score, or None.
+        nms_style: 'OR' or 'MERGE' (utils/nms/nms.py), handed to the NMS step."""
+        from ..utils.nms.nms import check_nms_style, nms_from_candidates
+        check_nms_style(nms_style)
         x = self._as_input(x)
         L = _lib.lib()
         dev = self.device
@@ -376,7 +378,7 @@ class HipEngine(object):
             rowid, o = self._cand_row[:m].sort()      # the reference's order: (image, row) ascending
             cand = self._cand[:m][o]
             return nms_from_candidates(torch.div(rowid, self.total_rows, rounding_mode='floor'), cand, self.bs, nms_thres,
-                                       nc=self.no - 6)
+                                       nc=self.no - 6, nms_style=nms_style)
 
     def __call__(self, x):
         x = self._as_input(x)

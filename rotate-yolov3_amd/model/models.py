@@ -371,16 +371,17 @@ class Darknet(nn.Module):
             self._engines[key] = eng
         return eng
 
-    def detect(self, x, conf_thres=0.5, nms_thres=0.5):
+    def detect(self, x, conf_thres=0.5, nms_thres=0.5, nms_style='OR'):
         """Inference step = forward + the reference's non_max_suppression (utils/nms/nms.py:4-69), same return value.
         On the GPU (eval mode, HIP backend) the yolo layers run the fused decode + confidence filter + compaction kernel
         and every (image, class) set goes through one segmented rotated-NMS launch (HipEngine.detect); elsewhere it is
-        literally non_max_suppression(self(x)[0], ...)."""
-        from ..utils.nms.nms import non_max_suppression
+        literally non_max_suppression(self(x)[0], ...).  nms_style: 'OR' or 'MERGE' (utils/nms/nms.py), handed through."""
+        from ..utils.nms.nms import check_nms_style, non_max_suppression
+        check_nms_style(nms_style)
         if self.backend == 'torch' or not x.is_cuda or self.training:
-            return non_max_suppression(self(x)[0], conf_thres, nms_thres)
+            return non_max_suppression(self(x)[0], conf_thres, nms_thres, nms_style)
         self._drop_stale_eval_engines()
-        return self.engine(x.shape, x.device).detect(x, conf_thres, nms_thres)
+        return self.engine(x.shape, x.device).detect(x, conf_thres, nms_thres, nms_style=nms_style)
 
     def _drop_stale_eval_engines(self):
         """The eval engines hold packed bf16 copies of the weights and the folded BatchNorm: rebuilt when anything changed since

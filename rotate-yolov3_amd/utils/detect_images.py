@@ -13,7 +13,7 @@ import torch
 
 from ..model import hip_ops
 from .datasets import letterbox_batch
-from .nms.nms import _flat, nms_from_candidates
+from .nms.nms import _flat, check_nms_style, nms_from_candidates
 
 
 def rescale_geometry(shapes, size):
@@ -30,11 +30,15 @@ def _split(det, det_off, n):
     return [det[off[b]:off[b + 1]] if off[b + 1] > off[b] else None for b in range(n)]
 
 
-def detect_images(model, cache, n, shapes, img_sizes, conf_thres, nms_thres, scale_nms_thres=0.95, slots=None):
+def detect_images(model, cache, n, shapes, img_sizes, conf_thres, nms_thres, scale_nms_thres=0.95, slots=None, nms_style='OR'):
     """-> (output, det, det_off): list[n] of [k, 8] rows (x, y, w, h, a, score, class_conf, class) in ORIGINAL image pixels, rounded, by
     descending score (None: no detection); the same rows back to back, fp32 [M, 8]; their offsets, int32 [n + 1] on the device.
     cache: the device cache of the n images, shapes their (h, w); img_sizes: the network sizes; slots >= n: the engine's batch size (the
-    slots past n are border and their rows are dropped)."""
+    slots past n are border and their rows are dropped).
+    nms_style 'MERGE' (utils/nms/nms.py): with one size, that size's NMS; with several, the final NMS over the scales alone -- the
+    same object found at several sizes gives several estimates of one box, and the kept row becomes their score-weighted mean (not
+    rounded again); the per-size passes at scale_nms_thres only remove duplicates inside a scale and stay 'OR'."""
+    check_nms_style(nms_style)
     shapes = [tuple(int(v) for v in s) for s in shapes][:n]
     if len(shapes) != n or not img_sizes:
         raise ValueError("detect_images: %d shapes for %d images, sizes %r" % (len(shapes), n, list(img_sizes)))
@@ -44,7 +48,10 @@ def detect_images(model, cache, n, shapes, img_sizes, conf_thres, nms_thres, sca
     with torch.no_grad():
         for size in img_sizes:
             batch = letterbox_batch(cache, shapes, int(size), slots)
-            out = model.detect(batch, conf_thres, scale_nms_thres if multi else nms_thres)[:n]
+            if multi or nms_style == 'OR':
+                out = model.detect(batch, conf_thres, scale_nms_thres if multi else nms_thres)[:n]
+            else:
+                out = model.detect(batch, conf_thres, nms_thres, nms_style=nms_style)[:n]
             det, det_off = _flat(out, dev)
             hip_ops.det_rescale(det, det_off, torch.from_numpy(rescale_geometry(shapes, size)).to(dev))
             if not multi:
@@ -59,4 +66,4 @@ def detect_images(model, cache, n, shapes, img_sizes, conf_thres, nms_thres, sca
         cand, img = cand[ok], img[ok]
         if cand.shape[0] == 0:
             return [None] * n, torch.zeros(0, 8, device=dev), torch.zeros(n + 1, dtype=torch.int32, device=dev)
-        return nms_from_candidates(img, cand, n, nms_thres, flat=True)
+        return nms_from_candidates(img, cand, n, nms_thres, flat=True, nms_style=nms_style)

@@ -6,14 +6,30 @@
 Kept quirks of the reference: `prediction` is modified in place (pred[:, 5] *= class_conf, nms.py:35); boxes with
 w or h <= 2 px or any non-finite entry are dropped (:40); detections are NMS-ed per class with `r_nms` on the
 score-sorted rows (:57-66).  The three argsorts are stable here (ties keep the lower row first) so that the
-result is deterministic; the reference's are not (any tie order is a valid reference output).  The dead pure-Python branch (:71-144, with its live ipdb breakpoint) is not reproduced.
+result is deterministic; the reference's are not (any tie order is a valid reference output).
+
+nms_style: 'OR' (default: greedy NMS, the live branch) or 'MERGE', the `nms_style == 'MERGE'` case of the reference's dead pure-Python
+branch (:115-127): columns 0..4 of every kept row become the score-weighted mean of the rows it suppresses and itself
+(ryolo_rnms_merge_segmented, include/ryolo.h).  MERGE keeps exactly the rows OR keeps -- the IoU is the NMS kernel's fp32 arithmetic, not
+that branch's fp64 skew_bbox_iou -- and leaves score, class confidence and class alone; angles are averaged modulo pi around the kept
+box's.  The rest of that branch (:71-144: the 'AND' and 'SOFT' styles, its live ipdb breakpoint) is not reproduced: SOFT decays column
+4, which in the rotated row layout is the angle, and AND compares against a constant 0.5 and drops lone boxes.
 """
 import torch
 
-from .r_nms import r_nms, r_nms_segmented
+from .r_nms import r_nms, r_nms_merge_segmented, r_nms_segmented
+
+NMS_STYLES = ('OR', 'MERGE')
 
 
-def non_max_suppression(prediction, conf_thres=0.5, nms_thres=0.5):
+def check_nms_style(nms_style):
+    if nms_style not in NMS_STYLES:
+        raise ValueError("nms_style %r: 'OR' (greedy rotated NMS) or 'MERGE' (score-weighted mean of the suppressed boxes)" % (nms_style,))
+    return nms_style
+
+
+def non_max_suppression(prediction, conf_thres=0.5, nms_thres=0.5, nms_style='OR'):
+    check_nms_style(nms_style)
     min_wh = 2
     output = [None] * len(prediction)
     for image_i, pred in enumerate(prediction):
@@ -33,6 +49,14 @@ def non_max_suppression(prediction, conf_thres=0.5, nms_thres=0.5):
         for c in pred[:, -1].unique():
             dc = pred[pred[:, -1] == c]
             dc = dc[(-dc[:, 5]).argsort(stable=True)]
+            if nms_style == 'MERGE':                # one segment: this class
+                seg_off = torch.tensor([0, len(dc)], dtype=torch.int32, device=dc.device)
+                flags, merged, _ = r_nms_merge_segmented(dc[:, :6], seg_off, len(dc), nms_thres)
+                keep = flags.bool()
+                dc = dc[keep]
+                dc[:, :5] = merged[keep]
+                det_max.append(dc)
+                continue
             inds = r_nms(dc[:, :6], nms_thres)
             det_max.append(dc[inds.to(dc.device)])
         if len(det_max):
@@ -49,7 +73,7 @@ def _flat(output, device):
     return det, det_off.to(device)
 
 
-def non_max_suppression_batched(prediction, conf_thres=0.5, nms_thres=0.5, flat=False):
+def non_max_suppression_batched(prediction, conf_thres=0.5, nms_thres=0.5, flat=False, nms_style='OR'):
     """Same result as non_max_suppression (row for row, order included) for a GPU `prediction`, without the Python loop
     over images and classes: one vectorised filter over the whole batch, one stable (image, class, score) ordering, ONE
     segmented rotated-NMS launch over all (image, class) sets (r_nms_segmented), one final per-image score ordering.
@@ -57,8 +81,9 @@ def non_max_suppression_batched(prediction, conf_thres=0.5, nms_thres=0.5, flat=
     Like the reference it scales prediction[..., 5] by the class confidence in place (nms.py:35).
     flat=True returns (output, det, det_off): besides the list, the rows of all images back to back (det [M, 8]; the list's entries are
     slices of it) and their offsets (int32 [bs+1] on the device) -- the inputs of r_nms.eval_match, with no further host read."""
+    check_nms_style(nms_style)
     if not prediction.is_cuda:
-        output = non_max_suppression(prediction, conf_thres, nms_thres)
+        output = non_max_suppression(prediction, conf_thres, nms_thres, nms_style)
         return (output,) + _flat(output, prediction.device) if flat else output
     bs, n, no = prediction.shape
     output = [None] * bs
@@ -74,13 +99,15 @@ def non_max_suppression_batched(prediction, conf_thres=0.5, nms_thres=0.5, flat=
     img, row = idx[:, 0], idx[:, 1]
     rows = prediction[img, row]                                   # [M, no]
     cand = torch.cat((rows[:, :6], class_conf[img, row].unsqueeze(1), class_pred[img, row].unsqueeze(1).float()), 1)
-    return nms_from_candidates(img, cand, bs, nms_thres, nc=no - 6, flat=flat)
+    return nms_from_candidates(img, cand, bs, nms_thres, nc=no - 6, flat=flat, nms_style=nms_style)
 
 
-def nms_from_candidates(img, cand, bs, nms_thres, nc=None, flat=False):
+def nms_from_candidates(img, cand, bs, nms_thres, nc=None, flat=False, nms_style='OR'):
     """Second half of non_max_suppression for a whole batch.  cand [M, 8] = (x, y, w, h, a, score, class_conf, class)
     of the rows that passed the confidence filter, in (image, row) order (at least one row); img [M] their image index.
-    flat=True: (output, det, det_off) as non_max_suppression_batched describes."""
+    flat=True: (output, det, det_off) as non_max_suppression_batched describes.  nms_style 'MERGE': the same rows, columns 0..4 of each
+    replaced by the weighted mean of its group (module docstring)."""
+    check_nms_style(nms_style)
     output = [None] * bs
     cp = cand[:, 7].long()
     if nc is None:
@@ -96,8 +123,13 @@ def nms_from_candidates(img, cand, bs, nms_thres, nc=None, flat=False):
     max_len = int(counts.max())                                   #                                    -- host read
     seg_off = torch.zeros(counts.numel() + 1, dtype=torch.int32, device=det.device)
     seg_off[1:] = counts.cumsum(0)
-    keep = r_nms_segmented(det[:, :6].contiguous(), seg_off, max_len, nms_thres).bool()
-    det = det[keep]
+    if nms_style == 'MERGE':
+        flags, merged, _ = r_nms_merge_segmented(det[:, :6].contiguous(), seg_off, max_len, nms_thres)
+        keep = flags.bool()
+        det = torch.cat((merged[keep], det[keep][:, 5:]), 1)
+    else:
+        keep = r_nms_segmented(det[:, :6].contiguous(), seg_off, max_len, nms_thres).bool()
+        det = det[keep]
     dimg = img[order][keep]
     # per image: score descending; ties keep (class, row) order -- what the reference's final argsort gives on the
     # class-by-class concatenation

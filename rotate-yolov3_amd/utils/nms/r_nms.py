@@ -75,6 +75,35 @@ def r_nms_segmented(dets, seg_offsets, max_seg_len, threshold):
     return flags
 
 
+def r_nms_merge_segmented(dets, seg_offsets, max_seg_len, threshold):
+    """Weighted-merge rotated NMS of many independent sets in one call (ryolo_rnms_merge_segmented, include/ryolo.h): the input of
+    r_nms_segmented.  Returns (flags uint8 [M]: exactly r_nms_segmented's; merged fp32 [M, 5]: for a kept row the score-weighted mean
+    (cx, cy, w, h, a) of the rows it owns, itself included, zeros elsewhere; owner int32 [M]: the kept row a row belongs to, itself for a
+    kept one)."""
+    if not dets.is_cuda:
+        raise RuntimeError("dets must be a CUDAtensor ")
+    if dets.dtype != torch.float32 or dets.stride(1) != 1 or dets.stride(0) < 6:
+        dets = dets.float().contiguous()
+    m, S = dets.size(0), seg_offsets.numel() - 1
+    flags = torch.zeros(m, dtype=torch.uint8, device=dets.device)
+    merged = torch.zeros(m, 5, dtype=torch.float32, device=dets.device)
+    owner = torch.arange(m, dtype=torch.int32, device=dets.device)
+    if m == 0 or S <= 0:
+        return flags, merged, owner
+    seg_offsets = seg_offsets.to(device=dets.device, dtype=torch.int32).contiguous()
+    L = _lib.lib()
+    nbytes = L.ryolo_rnms_merge_segmented_workspace_bytes(m, S, int(max_seg_len))
+    if nbytes == 0:
+        _lib.check(-3, "ryolo_rnms_merge_segmented")
+    with torch.cuda.device(dets.device):
+        ws = _workspace(dets.device, nbytes)
+        _lib.check(L.ryolo_rnms_merge_segmented(dets.data_ptr(), m, dets.stride(0), seg_offsets.data_ptr(), S, int(max_seg_len),
+                                                float(threshold), flags.data_ptr(), owner.data_ptr(), merged.data_ptr(),
+                                                ws.data_ptr(), ws.numel(), _lib.stream_ptr(dets.device)),
+                   "ryolo_rnms_merge_segmented")
+    return flags, merged, owner
+
+
 def riou_pairs(box1, box2):
     """IoU(box1[i], box2[i]) with the arithmetic of devRotateIoU (kernel.cu:251-260); rows (cx,cy,w,h,a,...)."""
     b1, b2 = _rows(box1), _rows(box2)

@@ -18,16 +18,17 @@ if ROOT not in sys.path:
 import rotate_yolov3_amd  # noqa: E402,F401
 from rotate_yolov3_amd.model.models import Darknet  # noqa: E402
 from rotate_yolov3_amd.utils.metrics import ap_per_class, match_predictions, match_predictions_batched  # noqa: E402
+from rotate_yolov3_amd.utils.nms.nms import check_nms_style  # noqa: E402
 from rotate_yolov3_amd.utils.nms.nms import non_max_suppression_batched as non_max_suppression  # noqa: E402  (same rows, one segmented NMS launch per batch; CPU tensors take the loop)
 from rotate_yolov3_amd.utils.parse_config import hyp_parse  # noqa: E402
 from rotate_yolov3_amd.utils.synthetic import SyntheticLoader  # noqa: E402
 
 
-def _batch_stats(stats, inf_out, targets, width, height, iou_thres, conf_thres, nms_thres):
+def _batch_stats(stats, inf_out, targets, width, height, iou_thres, conf_thres, nms_thres, nms_style='OR'):
     """The statistics of one batch, appended to `stats` in the order of the per-image loop of test(): one NMS call, one matcher call, ONE
     device -> host transfer (flags, scores and classes of all predictions, and below them the image and class of every target)."""
     bs = len(inf_out)
-    output, det, det_off = non_max_suppression(inf_out, conf_thres=conf_thres, nms_thres=nms_thres, flat=True)
+    output, det, det_off = non_max_suppression(inf_out, conf_thres=conf_thres, nms_thres=nms_thres, flat=True, nms_style=nms_style)
     labels = targets.clone()
     labels[:, [2, 4]] *= width
     labels[:, [3, 5]] *= height
@@ -49,8 +50,10 @@ def _batch_stats(stats, inf_out, targets, width, height, iou_thres, conf_thres, 
 
 
 def test(cfg, hyp, weights=None, batch_size=16, img_size=608, iou_thres=0.5, conf_thres=0.001, nms_thres=0.5, model=None,
-         n_images=32, device=None, nc=None, batched_match=True, loader=None):
-    """loader: batches to evaluate (utils.datasets.LoadImagesAndLabels); None: n_images synthetic ones"""
+         n_images=32, device=None, nc=None, batched_match=True, loader=None, nms_style='OR'):
+    """loader: batches to evaluate (utils.datasets.LoadImagesAndLabels); None: n_images synthetic ones;
+    nms_style: 'OR' or 'MERGE' (utils/nms/nms.py)"""
+    check_nms_style(nms_style)
     device = device or torch.device('cuda:0')
     if model is None:
         model = Darknet(cfg, hyp)
@@ -69,9 +72,9 @@ def test(cfg, hyp, weights=None, batch_size=16, img_size=608, iou_thres=0.5, con
             _, _, height, width = imgs.shape
             inf_out, train_out = model(imgs)
             if batched_match:
-                seen += _batch_stats(stats, inf_out, targets, width, height, iou_thres, conf_thres, nms_thres)
+                seen += _batch_stats(stats, inf_out, targets, width, height, iou_thres, conf_thres, nms_thres, nms_style)
                 continue
-            output = non_max_suppression(inf_out, conf_thres=conf_thres, nms_thres=nms_thres)
+            output = non_max_suppression(inf_out, conf_thres=conf_thres, nms_thres=nms_thres, nms_style=nms_style)
             for si, pred in enumerate(output):
                 labels = targets[targets[:, 0] == si, 1:].clone()
                 nl = len(labels)
@@ -103,10 +106,10 @@ def test(cfg, hyp, weights=None, batch_size=16, img_size=608, iou_thres=0.5, con
     return (mp, mr, map_, mf1, 0., 0., 0.), maps
 
 
-if __name__ == '__main__':
-    from rotate_yolov3_amd.utils.cli import add_ignored, pick_device, report_ignored
-    from rotate_yolov3_amd.utils.parse_config import parse_data_cfg
-    parser = argparse.ArgumentParser(prog='test.py')                     # the reference's flags (test.py:206-216), same defaults
+def build_parser():
+    """-> (parser, names of the flags that are accepted and ignored)"""
+    from rotate_yolov3_amd.utils.cli import add_ignored
+    parser = argparse.ArgumentParser(prog='test.py')                   # the reference's flags (test.py:206-216), same defaults
     parser.add_argument('--hyp', type=str, default='cfg/ICDAR/hyp.py', help='hyper-parameter path')
     parser.add_argument('--cfg', type=str, default='cfg/ICDAR/yolov3_608_se.cfg', help='cfg file path')
     parser.add_argument('--data', type=str, default='data/icdar_13+15.data', help='*.data file path (`classes`; with --real-data also `valid`, the image list)')
@@ -119,7 +122,15 @@ if __name__ == '__main__':
     parser.add_argument('--device', default='', help="device id (i.e. 0 or 0,1); the evaluation path has no CPU fallback")
     parser.add_argument('--synthetic', type=int, default=32, help='synthetic images to evaluate (without --real-data)')
     parser.add_argument('--real-data', action='store_true', help='evaluate the `valid` image list of --data instead of synthetic images (needs Pillow)')
+    parser.add_argument('--nms-style', type=str, default='OR', choices=['OR', 'MERGE'], help='OR: greedy rotated NMS; MERGE: every kept box becomes the score-weighted mean of the boxes it suppresses')
     ignored = add_ignored(parser, [('--save-json', dict(action='store_true', help='save a cocoapi-compatible JSON results file'))])
+    return parser, ignored
+
+
+if __name__ == '__main__':
+    from rotate_yolov3_amd.utils.cli import pick_device, report_ignored
+    from rotate_yolov3_amd.utils.parse_config import parse_data_cfg
+    parser, ignored = build_parser()
     opt = parser.parse_args()
     print(opt)
     report_ignored(parser, opt, ignored)
@@ -135,4 +146,4 @@ if __name__ == '__main__':
         loader = LoadImagesAndLabels(parse_data_cfg(opt.data)['valid'], opt.img_size, opt.batch_size, augment=False, device=device)
     test(opt.cfg, hyp_parse(opt.hyp), weights, opt.batch_size, opt.img_size, opt.iou_thres, opt.conf_thres, opt.nms_thres,
          n_images=opt.synthetic, device=device,
-         nc=int(parse_data_cfg(opt.data)['classes']) if os.path.isfile(opt.data) else None, loader=loader)
+         nc=int(parse_data_cfg(opt.data)['classes']) if os.path.isfile(opt.data) else None, loader=loader, nms_style=opt.nms_style)

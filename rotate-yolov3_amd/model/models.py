@@ -423,9 +423,23 @@ class Darknet(nn.Module):
         ts = list(self.parameters()) + list(self.buffers())
         return (sum(t._version for t in ts), hash(tuple(t.data_ptr() for t in ts)))
 
-    def train_engine(self, x_shape, device):
-        from .train_engine import TrainEngine
+    def _train_key(self, x_shape, device):
+        """(cache key of the TrainEngine for what trains now, the frozen pattern or None): with everything trainable the plain key,
+        otherwise requires_grad of every parameter is part of it"""
         key = ('train', tuple(x_shape), device.index)
+        pattern = tuple(bool(q.requires_grad) for q in self.parameters())
+        return (key, None) if all(pattern) else (key + (pattern,), pattern)
+
+    def train_engine(self, x_shape, device):
+        """The TrainEngine of this input shape and of what trains NOW: requires_grad of every parameter is read here, at each training
+        forward (the engine plans its backward, buffers and gradient sink around it).  When the pattern changed since the last training
+        forward, the train engines of other patterns are dropped: they hold gigabytes and cannot be used concurrently (the fused loss
+        finds the new engine by its head tensors, model/loss_static.py)."""
+        from .train_engine import TrainEngine
+        key, pattern = self._train_key(x_shape, device)
+        if pattern != self.__dict__.get('_train_pattern'):
+            self._engines = {k: v for k, v in self._engines.items() if not (k and k[0] == 'train') or k[3:] == key[3:]}
+            self._train_pattern = pattern
         eng = self._engines.get(key)
         if eng is None:
             eng = TrainEngine(self, x_shape, device)

@@ -313,7 +313,7 @@ def plan_eval(defs, convs, yolos, N, H, W, stem_pair=True, head_decode=True, cin
 
 
 # ------------------------------------------------------------------------------------------------ training
-def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, cin=3, yolos=None, head_decode=True):
+def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, cin=3, yolos=None, head_decode=True, trainable=None):
     """TrainPlan(shapes, buffers, x, act, grd, forward, blocks, backward).  act[i] / grd[i]: activation / gradient view per layer
     (same concat / slice structure).  forward: (kind, layer, record) with kind =
       conv   a block: layer, desc, xin, xin_g (None for layer 0), y, dy, res, res_g, res_alias (the skip source's gradient IS dy),
@@ -325,7 +325,17 @@ def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, 
              half: training reads the activation from the modules)
       add    (a, b, y, a_g, b_g, dy)        up  (x, y, x_g, dy)        yolo  (head, head_g)
     blocks: the conv records.  backward: (kind, layer, flags) in launch order (forward reversed); flags say which gradient views the
-    entry is the FIRST to write (it overwrites, later ones accumulate): conv (res_g, xin_g), add (a_g, b_g), up x_g; yolo: head index."""
+    entry is the FIRST to write (it overwrites, later ones accumulate): conv (res_g, xin_g), add (a_g, b_g), up x_g; yolo: head index.
+
+    trainable: None (every parameter trains), or {layer: (weight, affine, slope)} -- which parameters of a `convolutional` block train:
+    Conv2d.weight; the conv bias or a BatchNorm weight / bias; the activation's slope (a layer that is missing trains nothing).  A layer
+    output NEEDS a gradient iff its block has a trainable parameter or one of its inputs needs one (conv input, shortcut source, route
+    source, upsample input: what autograd's requires_grad would say).  A gradient view nobody needs is None -- in act / grd and in
+    every record -- and has no buffer; `backward` keeps the entries whose output needs a gradient, with the FIRST flags computed over
+    those.  A conv record says what its entry launches: `bnbwd` (the BatchNorm / activation / bias backward that makes dz: the conv
+    branch needs a gradient; False only where a fused shortcut merely hands dy on to its skip source), `dgrad` (xin_g is needed) and
+    `wgrad` (Conv2d.weight trains).  Layer 0's one-pass backward IS its weight gradient: with the stem's weight frozen the block takes
+    the recompute backward with a dz of its own."""
     n = len(defs)
     if any(d['type'] == 'd-convolutional' or 'weight_from' in d for d in defs):
         # a sharer would train as a layer with weights of its own, BatchNorm and activation: a different network
@@ -341,6 +351,20 @@ def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, 
             raise Refused("training path: maxpool graphs (yolov3-tiny) cannot train in the reference either "
                           "(model/loss.py:248 hard-codes three heads)")
     readers = _readers(defs)
+    # which layer outputs need a gradient: one sweep in layer order (every input of a layer is an earlier layer)
+    owns = [trainable is None or any(trainable.get(i, ())) for i in range(n)]
+    need = [True] * n
+    if trainable is not None:
+        for i, d in enumerate(defs):
+            t = d['type']
+            if t == 'convolutional':
+                need[i] = owns[i] or (i > 0 and need[i - 1])
+            elif t == 'shortcut':
+                need[i] = need[i - 1] or need[_abs(i, int(d['from']))]
+            elif t == 'route':
+                need[i] = any(need[l] for l in _sources(i, d))
+            else:
+                need[i] = i > 0 and need[i - 1]
     fused_into, conv_res = {}, {}
     for i, d in enumerate(defs):
         if d['type'] == 'shortcut' and i > 0 and defs[i - 1]['type'] == 'convolutional' and readers[i - 1] == [i] \
@@ -351,29 +375,31 @@ def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, 
     buffers = []
     x = _new(buffers, 8, H, W)
 
-    def new_pair(c, h, w):
-        return _new(buffers, c, h, w), _new(buffers, c, h, w)
+    def new_pair(c, h, w, g=True):
+        return _new(buffers, c, h, w), (_new(buffers, c, h, w) if g else None)
 
     act, grd = [None] * n, [None] * n
     alias, concat = _routes(defs, shp)
     home = {}
     children = {}                        # concat gradient buffer -> the slices that live inside it
     for i, srcs in concat.items():
-        act[i], grd[i] = new_pair(*shp[i])
+        act[i], grd[i] = new_pair(*shp[i], g=need[i])
         for src, off in srcs:
             if src in home or defs[src]['type'] not in ('convolutional', 'shortcut', 'upsample') or shp[src][0] % 8 or off % 8:
                 raise Refused("training path: route %d needs a copy (unsupported graph)" % i)
-            home[src] = (_slice(act[i], off, shp[src][0]), _slice(grd[i], off, shp[src][0]))
-            children.setdefault(grd[i], []).append(home[src][1])
+            home[src] = (_slice(act[i], off, shp[src][0]), _slice(grd[i], off, shp[src][0]) if need[src] else None)
+            if need[src]:
+                children.setdefault(grd[i], []).append(home[src][1])
 
     def pair_for(i):
-        return home[i] if i in home else new_pair(*shp[i])
+        return home[i] if i in home else new_pair(*shp[i], g=need[i])
 
     forward, blocks = [], []
+    fin_g = {}                           # layer -> the gradient view of the block that computes it (a conv with its fused shortcut)
     for i, d in enumerate(defs):
         t = d['type']
         if i in fused_into:
-            act[i], grd[i] = act[fused_into[i]], grd[fused_into[i]]
+            act[i], grd[i] = act[fused_into[i]], fin_g[i]    # (the conv's own grd is None where only the skip source needs dy)
             continue
         if t == 'convolutional':
             cv = convs[i]
@@ -381,22 +407,24 @@ def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, 
                 raise Refused(cv['refuse'])
             xin, xin_g = (x, None) if i == 0 else (act[i - 1], grd[i - 1])
             final = i + 1 if i in conv_res else i
-            y, dy = pair_for(final)
             # residual chain: the gradient of this block's output and of its skip source are the same tensor
             # (d(x + f(x)) passes dy to the skip branch unchanged) -- share ONE buffer instead of copying dy into the
             # source's gradient: the block reads dy before the branch's dgrad accumulates onto it (launch order)
-            res_alias = False
-            if i in conv_res and final not in home:
-                rg = grd[conv_res[i]]
-                if rg is not None and rg[2:5] == dy[2:5] and rg.cs == rg.C:
-                    dy, res_alias = rg, True
-            act[i], grd[i] = y, dy
+            rg = grd[conv_res[i]] if (i in conv_res and final not in home and need[final]) else None
+            res_alias = rg is not None and rg[2:5] == shp[final] and rg.cs == rg.C
+            if res_alias:
+                y, dy = _new(buffers, *shp[final]), rg            # (no gradient buffer of its own)
+            else:
+                y, dy = pair_for(final)
+            fin_g[final] = dy
+            act[i], grd[i] = y, (dy if need[i] else None)
             c, h, w = shp[i]
             desc = (N, xin.H, xin.W, xin.C, c, cv['k'], cv['s'], cv['pad'], xin.cs, c, 0, 0, 0.0, 1, 0)
             # layer 0 trains without its conv output: z0 (4 x the input, 27 MACs per value) is recomputed in the BatchNorm
             # passes instead of being stored and re-read (include/ryolo.h: ryolo_conv0_*); its one-pass backward never materialises dz
             recompute = bool(i == 0 and cv['bn'] and i not in conv_res and conv0_recompute
                              and _query('ryolo_conv0_recompute_supported', desc))
+            wgrad = bool(need[i] and (trainable is None or trainable.get(i, (False,))[0]))
             head_fused = None
             if (head_decode and yolos is not None and i + 1 < n and defs[i + 1]['type'] == 'yolo' and readers[i] == [i + 1] and i not in home
                     and i not in conv_res and not cv['bn'] and cv['k'] == 1 and cv['s'] == 1 and c % 8 == 0):
@@ -406,7 +434,8 @@ def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, 
                     head_fused = dict(desc=ht, na=int(na), no=int(no))
             blk = dict(layer=i, desc=desc, xin=xin, xin_g=xin_g, y=y, dy=dy, res=act[conv_res[i]] if i in conv_res else None,
                        res_g=grd[conv_res[i]] if i in conv_res else None, res_alias=res_alias, bn=cv['bn'], act=cv['act'], shape=shp[i],
-                       recompute=recompute, one_pass=bool(recompute and xin_g is None and conv0_one_pass), head_fused=head_fused)
+                       recompute=recompute, one_pass=bool(recompute and xin_g is None and conv0_one_pass and wgrad), head_fused=head_fused,
+                       bnbwd=need[i], dgrad=bool(need[i] and xin_g is not None), wgrad=wgrad)
             blocks.append(blk)
             forward.append(('conv', i, blk))
         elif t == 'shortcut':
@@ -436,16 +465,18 @@ def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, 
     heads = [i for kind, i, _ in forward if kind == 'yolo']
     backward = []
     for kind, i, pl in reversed(forward):
+        if not need[i + 1 if (kind == 'conv' and i in conv_res) else i]:
+            continue                                              # nobody needs a gradient this entry could write
         if kind == 'yolo':
             first(pl[1])                                          # always the first (sole) writer of the head gradient
             backward.append((kind, i, heads.index(i)))
         elif kind == 'conv':
             res_first = first(pl['res_g']) if (pl['res_g'] is not None and not pl['res_alias']) else None
-            backward.append((kind, i, (res_first, first(pl['xin_g']) if pl['xin_g'] is not None else None)))
+            backward.append((kind, i, (res_first, first(pl['xin_g']) if pl['dgrad'] else None)))
         elif kind == 'add':
-            backward.append((kind, i, (first(pl[3]), first(pl[4]))))
+            backward.append((kind, i, tuple(first(g) if g is not None else None for g in pl[3:5])))
         elif kind == 'up':
-            backward.append((kind, i, first(pl[2])))
+            backward.append((kind, i, first(pl[2]) if pl[2] is not None else None))
     return TrainPlan(shp, buffers, x, act, grd, forward, blocks, backward)
 
 
@@ -456,12 +487,14 @@ def reduce_fusion_pairs(tp):
     activation lets X's data gradient carry the reduce (ryolo_conv2d_dgrad_bnreduce, `rows` partial sums) is the caller's half."""
     by = {b['layer']: b for b in tp.blocks}
     pairs = []
-    for (k0, i0, _), (k1, i1, _) in zip(tp.backward[:-1], tp.backward[1:]):
-        if k0 != 'conv' or k1 != 'conv':
+    runs = set((k, i) for k, i, _ in tp.backward)
+    order = [(k, i) for k, i, _ in reversed(tp.forward)]      # neighbours in the WHOLE list: a frozen pattern keeps a subset of the pairs
+    for (k0, i0), (k1, i1) in zip(order[:-1], order[1:]):
+        if k0 != 'conv' or k1 != 'conv' or (k0, i0) not in runs or (k1, i1) not in runs:
             continue
         x, y = by[i0], by[i1]
         g, dy = x['xin_g'], y['dy']
-        if g is None or not y['bn'] or y['recompute'] or g != dy or dy[2:5] != y['shape'] or g.cs != g.C:
+        if not x['dgrad'] or not y['bnbwd'] or not y['bn'] or y['recompute'] or g != dy or dy[2:5] != y['shape'] or g.cs != g.C:
             continue
         rows = _query('ryolo_conv2d_dgrad_bnreduce_rows', x['desc'])
         if rows > 0:

@@ -73,12 +73,18 @@ class TrainEngine(object):
         # ---- the plan (model/plan.py): shapes, activation / gradient buffers (same concat / slice structure), blocks, who writes first.
         # RYOLO_CONV0_RECOMPUTE=0 stores layer 0's conv output like any other, RYOLO_CONV0_ONE_PASS=0 keeps its dz and weight gradient
         convs = {i: self._conv_attrs(mods[i]) for i, d in enumerate(defs) if d['type'] == 'convolutional'}
+        # requires_grad is the engine's only selector of what trains (as for autograd), read now: Darknet.train_engine() keys its cache by
+        # the pattern, so an engine never sees it change.  A frozen parameter is in no sink, no segment and gets no .grad; the plan drops
+        # every backward launch, gradient buffer and workspace that only served frozen parameters (model/plan.py: `trainable`)
+        self.tparams = [q for q in model.parameters() if q.requires_grad]
+        self._tset = set(self.tparams)
+        trainable = None if len(self.tparams) == sum(1 for _ in model.parameters()) else {i: self.block_trainable(mods[i]) for i in convs}
         # RYOLO_HEAD_DECODE=0 (the inference engine's switch) keeps a YOLO head's conv and its decode as two launches here too
         tp = self._tplan = plan.plan_train(defs, convs, self.bs, self.H, self.W,
                                            conv0_recompute=os.environ.get('RYOLO_CONV0_RECOMPUTE', '1') != '0',
                                            conv0_one_pass=os.environ.get('RYOLO_CONV0_ONE_PASS', '1') != '0', cin=cin,
                                            yolos={i: (mods[i].na, model.nc + 6) for i, d in enumerate(defs) if d['type'] == 'yolo'},
-                                           head_decode=os.environ.get('RYOLO_HEAD_DECODE', '1') != '0')
+                                           head_decode=os.environ.get('RYOLO_HEAD_DECODE', '1') != '0', trainable=trainable)
         self.shp = tp.shapes
 
         def new_buf(c, h, w):
@@ -95,6 +101,8 @@ class TrainEngine(object):
         self.x_nhwc = tv(tp.x)
         cmax = max(ops.cpad(max(c.out_channels, c.in_channels)) for c in (HipEngine._conv_of(mods[i]) for i in convs))
         self.ones = torch.ones(cmax, device=device)
+        # where the kernels leave the per-channel sums of a frozen BatchNorm weight / bias, conv bias or slope: never flushed, never read
+        self.dump = torch.zeros((3, cmax), device=device) if trainable is not None else None
         self.zeros = torch.zeros(cmax, device=device)
         self.stat_part = torch.zeros((tr.stat_rows(), 2, cmax), dtype=torch.float64, device=device)
         self.blocks = []                     # per conv: dict of tensors / modules
@@ -115,18 +123,20 @@ class TrainEngine(object):
                 if bn is not None:
                     z = None if rec['recompute'] else new_buf(c, h, w)
                     # (layer 0's one-pass backward never materialises dz: 1.5 GB at bs 64 / 608^2)
-                    dz = None if rec['one_pass'] else new_buf(c, h, w)
+                    dz = None if (rec['one_pass'] or not rec['bnbwd']) else new_buf(c, h, w)
                 else:
                     z, dz = y, dy            # linear bias conv: y IS z, dz IS dy
                 blk = dict(i=i, conv=conv, bn=bn, act=actmod[-1] if actmod else None, mish=any(type(s_).__name__ == 'Mish' for s_ in mods[i]),
                            xin=xin, xin_g=tv(rec['xin_g']), z=z, dz=dz, y=y, dy=dy, desc=desc, res=tv(rec['res']), res_g=tv(rec['res_g']),
                            res_alias=rec['res_alias'], cin_k=xin.shape[-1], k=desc.ksize, s=desc.stride, pad=desc.pad,
-                           npix=self.bs * h * w, C=c, recompute=rec['recompute'])
+                           npix=self.bs * h * w, C=c, recompute=rec['recompute'], bnbwd=rec['bnbwd'], dgrad=rec['dgrad'], wgrad=rec['wgrad'])
                 # a linear head conv the plan marked: conv + p rows + head-tensor store in one launch, issued at the yolo entry
                 if rec.get('head_fused') and not actmod and not blk['mish']:
                     blk['head_fused'] = rec['head_fused']
-                wgrad_ws = max(wgrad_ws, tr.wgrad_ws_bytes(desc))
-                bn_ws = max(bn_ws, tr.bn_bwd_ws_bytes(blk['npix'], c))
+                if rec['wgrad']:
+                    wgrad_ws = max(wgrad_ws, tr.wgrad_ws_bytes(desc))
+                if rec['bnbwd']:
+                    bn_ws = max(bn_ws, tr.bn_bwd_ws_bytes(blk['npix'], c))
                 self.blocks.append(blk)
                 fwd.append(('conv', i, blk))
             elif kind in ('add', 'up'):
@@ -146,7 +156,9 @@ class TrainEngine(object):
                 if hb is not None and (hb['head_fused']['na'], hb['head_fused']['no']) != (m.na, model.nc + 6):
                     hb.pop('head_fused')
                     hb = None
-                fwd.append(('yolo', i, (tv(rec[0]), tv(rec[1]), m, anchors, pbuf, io, h, w, hb)))
+                # a head nothing trainable feeds needs no gradient (the plan has none): the loss still writes one, into a scratch of the engine's
+                head_g = tv(rec[1]) if rec[1] is not None else new_buf(c, h, w)
+                fwd.append(('yolo', i, (tv(rec[0]), head_g, m, anchors, pbuf, io, h, w, hb)))
         # (head activation, head gradient) NHWC bf16 pairs in the order of self.p: the fused loss writes the gradients directly
         self.head_pairs = [(pl[0], pl[1]) for kind, _, pl in fwd if kind == 'yolo']
         self.fused_nhwc = False
@@ -166,8 +178,8 @@ class TrainEngine(object):
         for k, (hd, _) in enumerate(self.head_pairs):
             for b in self.blocks:
                 i = b['i']
-                if (b['y'] is hd and b['bn'] is None and b['conv'].bias is not None and i + 1 < len(defs) and defs[i + 1]['type'] == 'yolo'
-                        and readers[i] == [i + 1]):
+                if (b['y'] is hd and b['bn'] is None and b['conv'].bias is not None and b['conv'].bias in self._tset and i + 1 < len(defs)
+                        and defs[i + 1]['type'] == 'yolo' and readers[i] == [i + 1]):
                     b['head_k'] = k
         # (weight gradients on a second stream -- a parallel branch of the backward graphs -- were measured in rounds 2 and 5 and lost both
         #  times: 63.2 vs 62.6 ms, 50.07 vs 49.57 ms; wgrad_wide's two workgroups per CU fill the register file, nothing co-resides with it.
@@ -182,8 +194,19 @@ class TrainEngine(object):
         self._ws_w = None
         self.ws_b = torch.empty(max(bn_ws, 256), dtype=torch.uint8, device=device)
 
-        # ---- backward launch list: the forward entries reversed, each with its static accumulate flags (first contribution overwrites)
-        self.bplan = [(kind, i, pl, flags) for (kind, i, pl), (_, _, flags) in zip(reversed(fwd), tp.backward)]
+        # ---- backward launch list: the forward entries reversed -- those whose output needs a gradient -- each with its static accumulate
+        # flags (first contribution overwrites)
+        entries = {(kind, i): pl for kind, i, pl in fwd}
+        self.bplan = [(kind, i, entries[(kind, i)], flags) for kind, i, flags in tp.backward]
+
+    @staticmethod
+    def block_trainable(m):
+        """(weight, affine, slope) of a `convolutional` block for plan_train's `trainable`: does Conv2d.weight train; the conv bias or a
+        BatchNorm weight / bias; the activation's slope"""
+        conv, bn = HipEngine._conv_of(m), HipEngine._bn_of(m)
+        affine = [q for q in (conv.bias,) + ((bn.weight, bn.bias) if bn is not None else ()) if q is not None]
+        slopes = [q for s_ in m if isinstance(s_, nn.PReLU) for q in s_.parameters()]
+        return (bool(conv.weight.requires_grad), any(q.requires_grad for q in affine), any(q.requires_grad for q in slopes))
 
     @staticmethod
     def _conv_attrs(m):
@@ -208,7 +231,7 @@ class TrainEngine(object):
     #           was None, the replacement's values copied in otherwise (_check_direct_sink, _flush_param_grads): the sink,
     #           the captured graphs and the reducer's buckets stay as they are, and the all-reduce still sends this gradient.
     def _build_grad_sink(self):
-        plist = [q for q in self.model.parameters()]
+        plist = self.tparams
         views = getattr(self.model, '_dp_grad_views', None)
         ok = views is not None and os.environ.get("RYOLO_DIRECT_GRADS", "1") != "0"
         if ok:
@@ -259,7 +282,9 @@ class TrainEngine(object):
             warnings.warn("TrainEngine: %d param.grad tensors had been replaced (zero_grad(set_to_none=True)?) while a GradientAllReducer "
                           "owns them; they were re-bound to the reducer's buckets.  Use reducer.zero_grad() to clear gradients." % rebound)
 
-    def _grad_of(self, p):
+    def _grad_of(self, p, row=0):
+        if p not in self._tset:
+            return self.dump[row]            # frozen: the kernel's sums go nowhere (row: BatchNorm weight 0, bias 1, slope 2)
         g = self.static_grad.get(p)
         if g is None:
             self._build_grad_sink()
@@ -318,7 +343,7 @@ class TrainEngine(object):
     @staticmethod
     def _has_wgrad(b):
         """False for layer 0 when its whole backward is the one-pass kernel (csrc/conv0_bwd.hip: no dz, no separate weight gradient)"""
-        return not (b['bn'] is not None and b['recompute'] and b['xin_g'] is None and b['dz'] is None)
+        return b.get('wgrad', True) and not (b['bn'] is not None and b['recompute'] and b['xin_g'] is None and b['dz'] is None)
 
     @property
     def ws_w(self):
@@ -371,7 +396,8 @@ class TrainEngine(object):
             if kind == 'conv':
                 for q in list(pl['conv'].parameters()) + (list(pl['bn'].parameters()) if pl['bn'] is not None else []) + (
                         list(pl['act'].parameters()) if isinstance(pl['act'], nn.Module) else []):
-                    pos[q] = k
+                    if q in self._tset:
+                        pos[q] = k
         cuts = set()
         for bucket in getattr(self.model, '_dp_buckets', None) or []:
             ks = [pos[q] for q in bucket if q in pos]
@@ -451,7 +477,7 @@ class TrainEngine(object):
                 cout, cin, k, _ = w.shape
                 pl['packed'] = torch.empty(L.ryolo_conv_packed_weight_bytes(cout, pl['cin_k'], k), dtype=torch.uint8, device=dev)
                 pl['packed_d'] = torch.empty(L.ryolo_conv_packed_dgrad_bytes(cout, cin, k, pl['s']), dtype=torch.uint8,
-                                             device=dev) if pl['xin_g'] is not None else None
+                                             device=dev) if pl['dgrad'] else None
                 self.packs.add(w.detach(), pl['s'], pl['cin_k'], pl['packed'], pl['packed_d'])
             self.packs.finalize()
         self.packs.run()
@@ -535,7 +561,8 @@ class TrainEngine(object):
                 if self.fused_nhwc and g is not None:
                     buf.zero_()                               # keep the fused loss's scratch invariant (all zero)
             self._check_direct_sink()
-            self._grad_of(next(self.model.parameters()))     # make sure the gradient sink exists
+            if self.tparams:
+                self._grad_of(self.tparams[0])               # make sure the gradient sink exists
             segs = self._segments()
             if self.batch_reduce:
                 self._ensure_reduce_batches(segs)
@@ -567,6 +594,8 @@ class TrainEngine(object):
         pgrads = self.static_pg
         if lo == 0 and self.static_flat is not None:
             self.static_flat.zero_()
+        if lo == 0 and self.dump is not None:
+            self.dump.zero_()
         if not self._red_planned:
             self._plan_reduce_fusion()
         hook = getattr(self, 'backward_hook', None)           # tests: called before / after every entry of the launch list (eager launches only)
@@ -581,40 +610,44 @@ class TrainEngine(object):
                 dy = b['dy']
                 if b['res_g'] is not None and not b['res_alias']:   # fused shortcut: the skip branch receives dy unchanged
                     self._passthrough(dy, b['res_g'], res_first)
+                if not b['bnbwd']:
+                    return                                    # only the skip source needed dy
                 if bn is not None:
-                    dsl = self._grad_of(b['act'].weight) if isinstance(b['act'], nn.PReLU) else None
+                    dsl = self._grad_of(b['act'].weight, 2) if isinstance(b['act'], nn.PReLU) else None
                     if b['recompute'] and b['xin_g'] is None and b['dz'] is None:
                         # layer 0: BatchNorm / activation backward AND the weight gradient in one pass over dy (csrc/conv0_bwd.hip), no dz
                         if 'ws0f' not in b:
                             b['ws0f'] = tr.conv0_bn_bwd_wgrad_ws(dev)
                         tr.conv0_bn_bwd_wgrad(b['desc'], b['xin'], b['packed'], dy, b['stats'], b['actcode'], b['slope'],
-                                              self._grad_of(bn.weight), self._grad_of(bn.bias), dsl, self._grad_of(conv.weight),
+                                              self._grad_of(bn.weight, 0), self._grad_of(bn.bias, 1), dsl, self._grad_of(conv.weight),
                                               conv.in_channels, True, b['ws0f'])
                         return
                     elif b['recompute']:
                         if 'ws0' not in b:
                             b['ws0'] = tr.conv0_bn_bwd_ws(dev)
                         tr.conv0_bn_bwd(b['desc'], b['xin'], b['packed'], dy, b['stats'], b['actcode'], b['slope'], b['dz'],
-                                        self._grad_of(bn.weight), self._grad_of(bn.bias), dsl, b['ws0'])
+                                        self._grad_of(bn.weight, 0), self._grad_of(bn.bias, 1), dsl, b['ws0'])
                     elif b.get('red_part') is not None:       # the reduce pass ran inside the data gradient that produced dy
                         tr.bn_act_bwd_reduced(b['z'], dy, b['stats'], 1, b['slope'], b['dz'],
-                                              self._grad_of(bn.weight), self._grad_of(bn.bias), dsl, b['red_part'], self.ws_b)
+                                              self._grad_of(bn.weight, 0), self._grad_of(bn.bias, 1), dsl, b['red_part'], self.ws_b)
                     else:
                         tr.bn_act_bwd(b['z'], dy, b['stats'], b['actcode'], b['slope'], b['dz'],
-                                      self._grad_of(bn.weight), self._grad_of(bn.bias), dsl, self.ws_b)
-                elif conv.bias is not None:
+                                      self._grad_of(bn.weight, 0), self._grad_of(bn.bias, 1), dsl, self.ws_b)
+                elif conv.bias is not None and conv.bias in self._tset:
                     hk = b.get('head_k')
                     if hk is not None and self._fold_now[hk]:
                         # the loss's dense pass summed the head gradient while storing it: finalise its rows (x the upstream gradient)
                         tr.head_bias_finalize(self._bias_parts[hk], b['npix'], b['C'], self.head_gscale, self._grad_of(conv.bias), self._bias_ws)
                     else:
                         tr.bn_act_bwd(b['z'], dy, None, 0, None, None, None, self._grad_of(conv.bias), None, self.ws_b)
-                if self.batch_reduce:
+                if not b['wgrad']:
+                    pass                                      # a frozen Conv2d.weight: no weight gradient at all
+                elif self.batch_reduce:
                     # partial tiles only, into the layer's own workspace; the segment's reduces run as one launch below
                     tr.conv_wgrad_partials(b['desc'], b['xin'], b['dz'], conv.in_channels, self._grad_of(conv.weight), True, b['ws_w'])
                 else:
                     tr.conv_wgrad(b['desc'], b['xin'], b['dz'], conv.in_channels, self._grad_of(conv.weight), True, self.ws_w)
-                if b['xin_g'] is not None:
+                if b['dgrad']:
                     y = b.get('red_for')
                     if y is not None:     # 1x1 data gradient + the reduce pass of the block whose output this conv consumed
                         tr.conv_dgrad_bnreduce(b['desc'], b['dz'], b['packed_d'], self.ones, self.zeros, b['xin_g'], not in_first,
@@ -623,10 +656,12 @@ class TrainEngine(object):
                         tr.conv_dgrad(b['desc'], b['dz'], b['packed_d'], self.ones, self.zeros, b['xin_g'], not in_first)
             elif kind == 'add':
                 dyv = pl[5]
-                self._passthrough(dyv, pl[3], flags[0])
-                self._passthrough(dyv, pl[4], flags[1])
+                for g, is_first in zip(pl[3:5], flags):
+                    if g is not None:
+                        self._passthrough(dyv, g, is_first)
             elif kind == 'up':
-                tr.upsample2x_bwd(pl[3], pl[2], not flags)
+                if pl[2] is not None:
+                    tr.upsample2x_bwd(pl[3], pl[2], not flags)
 
         for kind, i, pl, flags in self.bplan[lo:hi]:
             if hook is not None:
@@ -672,5 +707,5 @@ class TrainEngine(object):
                                         dst.stride(2), n * h * w, c, _lib.stream_ptr(self.device)), "ryolo_add_nhwc")
 
     def __call__(self, x):
-        anchor = next(self.model.parameters())        # makes the Function part of the autograd graph
+        anchor = self.tparams[0] if self.tparams else next(self.model.parameters())   # makes the Function part of the autograd graph
         return list(_Fn.apply(self, x, anchor))

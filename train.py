@@ -17,6 +17,8 @@ the way to train a "matrix" cfg (weight_from / d-convolutional layers), which th
 its dilated shared 3x3 layers on the HIP kernels (model.shared_conv_backend, hip_train_ops.SharedDilatedConv).  The se cfgs train the
 same way: `--backend torch`, and `--se hip` runs their squeeze-and-excitation layers, forward and backward, on the HIP kernels
 (model.se_backend, hip_train_ops.SqueezeExcite).
+`--transfer` / `--prebias` freeze as the reference does (train.py:120-135; freeze_for_transfer below); on the HIP backend requires_grad is all
+the TrainEngine needs to leave out the frozen layers' backward, gradient buffers and workspaces.
 Per-epoch evaluation follows the reference's gate (train.py:306-314: test.test(model=model) every `test_interval`
 epochs from epoch 10 on, always considered at the final epoch unless --notest), `last.pt` is written every epoch and
 `best.pt` when the mAP fitness does not decrease (train.py:345-357).
@@ -76,11 +78,55 @@ def lr_factor(epoch, epochs, multiplier, warm_epoch):
     return f
 
 
-def init_schedule(optimizer, hyp):
+def init_schedule(optimizer, hyp, scale=1.0):
     """The schedule multiplies lr0 -- never the lr a restored optimizer state carries (that one was already scaled by the
-    factor of the epoch it was saved in; the reference's schedulers keep `initial_lr` for the same reason)."""
+    factor of the epoch it was saved in; the reference's schedulers keep `initial_lr` for the same reason).  scale: the x100 of
+    --transfer / --prebias (freeze_for_transfer), which the reference applies before it builds its schedulers (train.py:123-127, :143)."""
     for g in optimizer.param_groups:
-        g['initial_lr'] = float(hyp['lr0'])
+        g['initial_lr'] = float(hyp['lr0']) * scale
+
+
+TRANSFER_LR_SCALE, TRANSFER_MOMENTUM_SCALE = 100.0, 0.9
+
+
+def freeze_for_transfer(model, optimizer, transfer=False, prebias=False):
+    """--transfer / --prebias (reference train.py:120-135): nf = filters of the conv in front of the first yolo layer; --prebias trains
+    the parameters with numel() == nf (the head biases), --transfer those with shape[0] == nf (head weights and biases) and everything
+    else is frozen -- quirk included: any other tensor of that leading size trains too.  The fewer parameters allow more aggressive
+    settings: lr x100 on every group, momentum x0.9 where a group has one (SGD, not Adam).  Returns the trainable parameters.
+    On the HIP backend requires_grad is all the TrainEngine needs: it skips every backward launch that only served frozen layers."""
+    nf = int(model.module_defs[model.yolo_layers[0] - 1]['filters'])
+    for g in optimizer.param_groups:
+        g['lr'] *= TRANSFER_LR_SCALE
+        if g.get('momentum') is not None:
+            g['momentum'] *= TRANSFER_MOMENTUM_SCALE
+    kept = []
+    for p in model.parameters():
+        p.requires_grad = bool((prebias and p.numel() == nf) or (not prebias and transfer and p.shape[0] == nf))
+        if p.requires_grad:
+            kept.append(p)
+    return kept
+
+
+def print_model_biases(model, out=print):
+    """The reference's bias summary (utils/utils.py:369-380) of the conv in front of every yolo layer.  Its `view(3, -1)` predates the
+    72 anchors per head of the rotated cfgs: the bias is viewed by the head's own `na`, [na, 6 + nc], with columns 0:5 regression
+    (x, y, w, h, angle), 5 objectness, 6: classification."""
+    out('\nModel Bias Summary (per output layer):')
+    for l in model.yolo_layers:
+        b = model.module_list[l - 1][0].bias.detach().float().view(model.module_list[l].na, -1)
+        out('regression: %5.2f+/-%-5.2f ' % (b[:, :5].mean(), b[:, :5].std()) +
+            ' objectness: %5.2f+/-%-5.2f ' % (b[:, 5].mean(), b[:, 5].std()) +
+            ' classification: %5.2f+/-%-5.2f' % (b[:, 6:].mean(), b[:, 6:].std()))
+
+
+def create_backbone(f, out):
+    """The reference's create_backbone (utils/utils.py:390-401): checkpoint `f` without optimizer and results, epoch -1, written to `out`."""
+    x = torch.load(f, map_location='cpu')
+    x['optimizer'] = None
+    x['training_results'] = None
+    x['epoch'] = -1
+    torch.save(x, out)
 
 
 def set_epoch_lr(optimizer, hyp, epoch, epochs):
@@ -120,7 +166,7 @@ def train(opt, hyp):
     if 'pw' not in opt.arc:
         hyp['cls_pw'] = 1.
         hyp['obj_pw'] = 1.
-    epochs = int(opt.epochs or hyp['epochs'])
+    epochs = 1 if opt.prebias else int(opt.epochs or hyp['epochs'])      # reference train.py:38
     batch_size = int(opt.batch_size or hyp['batch_size'])
     init_seeds()
     nc = int(parse_data_cfg(opt.data)['classes']) if opt.data and os.path.isfile(opt.data) else 1
@@ -155,8 +201,15 @@ def train(opt, hyp):
             best_fitness = chkpt['best_fitness']
         if opt.resume:
             start_epoch = chkpt['epoch'] + 1
+    lr_scale = 1.0
+    if opt.transfer or opt.prebias:       # before the reducer: its buckets hold the parameters that train
+        kept = freeze_for_transfer(model, optimizer, opt.transfer, opt.prebias)
+        lr_scale = TRANSFER_LR_SCALE
+        if rank == 0:
+            print('%s: %d of %d parameter tensors train, lr x%g' % ('--prebias' if opt.prebias else '--transfer', len(kept),
+                                                                      sum(1 for _ in model.parameters()), lr_scale))
     dp = GradientAllReducer(model, bucket_mb=opt.bucket_mb)
-    init_schedule(optimizer, hyp)         # after load_state_dict: base lr = lr0, not the saved (already scaled) lr
+    init_schedule(optimizer, hyp, lr_scale)   # after load_state_dict: base lr = lr0 (x100 under --transfer / --prebias), not the saved lr
     if world > 1 and hasattr(optimizer, 'grad_scale'):
         # the all-reduce delivers the SUM over ranks; FusedSGD / FusedAdam apply 1/world while they read the gradient (no extra 250 MB pass)
         optimizer.grad_scale = 1.0 / world
@@ -206,7 +259,10 @@ def train(opt, hyp):
                 print(s)
         final_epoch = epoch + 1 == epochs
         # evaluation gate of the reference (train.py:306-314); --test-from overrides its hard-coded "not before epoch 10"
-        if not (opt.notest or (opt.nosave and epoch < opt.test_from)) or final_epoch:
+        if opt.prebias:
+            if rank == 0:
+                print_model_biases(model)     # reference train.py:306-307: no evaluation in the prebias pass
+        elif not (opt.notest or (opt.nosave and epoch < opt.test_from)) or final_epoch:
             if use_cuda and epoch >= opt.test_from and epoch % int(hyp.get('test_interval', 1)) == 0 and epoch != 0 and not opt.notest:   # the evaluation path (rotated-IoU matching) has no CPU fallback
                 import test as test_mod
                 with torch.no_grad():
@@ -220,7 +276,7 @@ def train(opt, hyp):
             fitness = results[2]          # mAP
             if fitness > best_fitness:
                 best_fitness = fitness
-            if not opt.nosave or final_epoch:
+            if not opt.nosave or final_epoch or opt.prebias:      # reference train.py:341
                 with open(results_file, 'r') as fh:
                     chkpt = {'epoch': epoch, 'best_fitness': best_fitness, 'training_results': fh.read(),
                              'model': model.state_dict(), 'optimizer': None if final_epoch else optimizer.state_dict()}
@@ -232,7 +288,11 @@ def train(opt, hyp):
                     torch.save(chkpt, os.path.join(opt.wdir, 'backup%g.pt' % epoch))
     if rank == 0:
         print('%g epochs completed in %.3f hours.\n' % (epochs - start_epoch, (time.time() - t0) / 3600))
+    if opt.prebias and rank == 0:         # reference train.py:415: the prebias pass ends as the backbone of the run that follows
+        create_backbone(os.path.join(opt.wdir, 'last.pt'), os.path.join(opt.wdir, 'backbone.pt'))
     if world > 1:
+        if opt.prebias:
+            dist.barrier()                # the other ranks load backbone.pt next
         dist.destroy_process_group()
     return results
 
@@ -276,11 +336,14 @@ def make_parser():
     parser.add_argument('--se', choices=['torch', 'hip'], default='torch',
                         help="model.se_backend: with --backend torch, run the se layers of an se cfg on the HIP kernels, forward and "
                              "backward ('hip'), or on the ATen chain ('torch')")
+    parser.add_argument('--transfer', action='store_true',
+                        help='transfer learning: train the convs in front of the yolo layers only, lr x100 (everything else is frozen; the '
+                             'HIP TrainEngine skips the frozen layers\' backward)')
+    parser.add_argument('--prebias', action='store_true',
+                        help='train the yolo biases alone for one epoch, write <wdir>/backbone.pt, then train normally from it')
     ignored = add_ignored(parser, [
         ('--multi-scale', dict(action='store_true', help='adjust (67%% - 150%%) img_size every 10 batches (the engine plans one input shape)')),
         ('--rect', dict(action='store_true', help='rectangular training (an image-loader mode)')),
-        ('--transfer', dict(action='store_true', help='transfer learning: train the yolo layers only (every layer trains here)')),
-        ('--prebias', dict(action='store_true', help='transfer-learn yolo biases prior to training (every layer trains here)')),
         ('--evolve', dict(action='store_true', help='evolve hyperparameters')),
         ('--bucket', dict(type=str, default='', help='gsutil bucket')),
         ('--img-weights', dict(action='store_true', help='select training images by weight')),
@@ -299,14 +362,24 @@ def parse_args(argv=None):
     return parser, ignored, opt
 
 
-if __name__ == '__main__':
+def main(argv=None):
     from rotate_yolov3_amd.utils.cli import report_ignored
-    parser, ignored, opt = parse_args()
+    parser, ignored, opt = parse_args(argv)
     if opt.resume:
         opt.weights = os.path.join(opt.wdir, 'last.pt')          # reference train.py:406
     print(opt)
     report_ignored(parser, opt, ignored)
     hyp = hyp_parse(opt.hyp)
-    train(opt, hyp)
-    if opt.name and int(os.environ.get('RANK', '0')) == 0 and os.path.isfile(results_file):
+    rank = int(os.environ.get('RANK', '0'))
+    if opt.prebias:                                              # reference train.py:413-417
+        train(opt, hyp)                                          # the yolo biases alone, one epoch; writes <wdir>/backbone.pt
+        opt.weights = os.path.join(opt.wdir, 'backbone.pt')
+        opt.prebias = False
+    results = train(opt, hyp)
+    if opt.name and rank == 0 and os.path.isfile(results_file):
         os.replace(results_file, 'results_%s.txt' % opt.name)    # reference train.py:366-368
+    return results
+
+
+if __name__ == '__main__':
+    main()

@@ -518,6 +518,7 @@ int ryolo_bn_act_fwd(const void *z, int z_cstride, const float *scale, const flo
                      const void *residual, int res_cstride, void *y, int y_cstride, long long npix, int C, void *stream) {
     if (!z || !scale || !shift || !y || npix <= 0 || C <= 0 || (C & 7) || (z_cstride & 7) || (y_cstride & 7))
         return RYOLO_EINVAL;
+    if (residual && (res_cstride & 7)) return RYOLO_EINVAL;    // read with the same 16-byte loads as z
     if (act < 0 || act > 2) return RYOLO_EINVAL;
     const bool ntl = nt_pass(0, npix, C);
 #define RYOLO_BN_FWD(A)                                                                                                   \

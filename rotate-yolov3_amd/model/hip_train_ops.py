@@ -26,26 +26,19 @@ def arc_flags(arc):
     raise ValueError("unknown arc %r" % (arc,))
 
 
-class WgradReduceBatch(object):
-    """The split-K reduces of several layers as one launch (csrc/wgrad.hip: wgrad_reduce_batch_kernel).  Every layer keeps its partial
-    tiles in its OWN workspace (conv_wgrad_partials); add() describes a layer's reduce, finalize() uploads the job table, run() reduces all
-    of them -- bit-identical to the per-layer reduces."""
+class _JobTable(object):
+    """Jobs of one batched launch: ctypes records of type `job` whose fill function left the job's block count in block_end.  finalize()
+    turns the counts into each job's range of the launch's blocks and uploads the table (from the host: outside any stream capture),
+    run() is the ONE launch of the entry point `entry`(table, n, total_blocks, stream)."""
+    job = entry = None
 
     def __init__(self, device):
         self.device = device
         self.jobs = []
         self.keep = []
 
-    def add(self, d, cin_real, ws, grad, accumulate):
-        j = WgradReduceJob()
-        n = _lib.lib().ryolo_conv_wgrad_reduce_job_fill(C.byref(j), C.byref(d), cin_real, ws.data_ptr(), grad.data_ptr(), 1 if accumulate else 0)
-        if n <= 0:
-            raise RuntimeError("ryolo_conv_wgrad_reduce_job_fill failed")
-        self.jobs.append(j)
-        self.keep.append((ws, grad))
-
     def finalize(self):
-        arr = (WgradReduceJob * len(self.jobs))()
+        arr = (self.job * len(self.jobs))()
         blk = 0
         for q, j in enumerate(self.jobs):
             nb = j.block_end
@@ -57,16 +50,27 @@ class WgradReduceBatch(object):
         self.n = len(self.jobs)
 
     def run(self):
-        _lib.check(_lib.lib().ryolo_conv_wgrad_reduce_batch(self.dev_jobs.data_ptr(), self.n, self.total_blocks, _s(self.device)),
-                   "ryolo_conv_wgrad_reduce_batch")
+        _lib.check(getattr(_lib.lib(), self.entry)(self.dev_jobs.data_ptr(), self.n, self.total_blocks, _s(self.device)), self.entry)
 
 
-class WeightPackBatch(object):
+class WgradReduceBatch(_JobTable):
+    """The split-K reduces of several layers as one launch (csrc/wgrad.hip: wgrad_reduce_batch_kernel).  Every layer keeps its partial
+    tiles in its OWN workspace (conv_wgrad_partials); add() describes a layer's reduce, finalize() uploads the job table, run() reduces all
+    of them -- bit-identical to the per-layer reduces."""
+    job, entry = WgradReduceJob, "ryolo_conv_wgrad_reduce_batch"
+
+    def add(self, d, cin_real, ws, grad, accumulate):
+        j = WgradReduceJob()
+        n = _lib.lib().ryolo_conv_wgrad_reduce_job_fill(C.byref(j), C.byref(d), cin_real, ws.data_ptr(), grad.data_ptr(), 1 if accumulate else 0)
+        if n <= 0:
+            raise RuntimeError("ryolo_conv_wgrad_reduce_job_fill failed")
+        self.jobs.append(j)
+        self.keep.append((ws, grad))
+
+
+class WeightPackBatch(_JobTable):
     """Every weight pack of a training step (forward layout + dgrad classes of each conv) as one launch."""
-
-    def __init__(self, device):
-        self.device = device
-        self.jobs = []
+    job, entry = PackJob, "ryolo_conv_pack_batch"
 
     def add(self, weight, stride, cin_pad, packed_fwd, packed_dgrad):
         cout, cin, k, _ = weight.shape
@@ -79,23 +83,6 @@ class WeightPackBatch(object):
             j = PackJob()
             C.memmove(C.byref(j), C.byref(tmp[q]), C.sizeof(PackJob))
             self.jobs.append(j)
-
-    def finalize(self):
-        arr = (PackJob * len(self.jobs))()
-        blk = 0
-        for q, j in enumerate(self.jobs):
-            nb = j.block_end
-            j.block_begin, j.block_end = blk, blk + nb
-            blk += nb
-            arr[q] = j
-        self.total_blocks = blk
-        raw = bytes(arr)
-        self.dev_jobs = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
-        self.n = len(self.jobs)
-
-    def run(self):
-        _lib.check(_lib.lib().ryolo_conv_pack_batch(self.dev_jobs.data_ptr(), self.n, self.total_blocks, _s(self.device)),
-                   "ryolo_conv_pack_batch")
 
 
 def _s(dev):

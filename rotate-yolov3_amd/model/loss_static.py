@@ -227,7 +227,7 @@ class FusedLoss(object):
         eng = self._engine_of(p)
         # an engine that launches eagerly because a capture failed or because RYOLO_NO_GRAPH=1 asked for it keeps the HIP loss kernels (launched
         # eagerly too); an engine BUILT without graphs (use_graph=False: tests, debugging) takes the eager mirror
-        eager_engine = eng is not None and not eng.use_graph and (eng.graph_fallback is not None or getattr(eng, 'no_graph_env', False))
+        eager_engine = eng is not None and not eng.use_graph and (eng.graph_fallback is not None or eng.no_graph_env)
         if eng is None or not (eng.use_graph or eager_engine):
             return None
         h = core.hyp if getattr(core, 'hyp', None) else hyp
@@ -235,7 +235,7 @@ class FusedLoss(object):
             return None                     # the tensor formulation has no rotated IoU: eager mirror (RotatedIoU autograd function)
         key = tuple(float(h[k]) for k in ('giou', 'cls', 'cls_pw', 'obj', 'obj_pw', 'iou_t', 'ang_t', 'reg')) + (
             float(hyp['context_factor']), float(h.get('riou', 0)), str(arc), float(h.get('fl_gamma', 0.0)))
-        st = getattr(eng, '_fused_state', None)
+        st = eng._fused_state
         if st is None or st['key'] != key:
             st = self._make_state(eng, hyp, key)
             eng._fused_state = st
@@ -282,17 +282,16 @@ class FusedLoss(object):
 
     def _make_state(self, eng, hyp, key):
         dev = eng.device
-        if not hasattr(eng, "static_pg"):
-            eng.static_pg = [torch.zeros_like(q) for q in eng.p]
+        pg = eng.head_grad_buffers()
         h = self.model.hyp if getattr(self.model, 'hyp', None) else hyp
-        pairs = getattr(eng, 'head_pairs', None)
-        nhwc = self.impl == 'hip' and pairs is not None and all(
+        pairs = eng.head_pairs
+        nhwc = self.impl == 'hip' and all(
             (hd.shape[-1] % 8 == 0 and q.shape[1] * q.shape[4] == hd.shape[-1]) for (hd, _), q in zip(pairs, eng.p))
         if nhwc:
             eng.fused_nhwc = True          # the engine's fp32 head-gradient buffers become all-zero scratch (see backward())
-            for buf in eng.static_pg:
+            for buf in pg:
                 buf.zero_()
-        return dict(key=key, hyp=dict(hyp), calls=0, graph=None, pg=eng.static_pg, eng=eng,
+        return dict(key=key, hyp=dict(hyp), calls=0, graph=None, pg=pg, eng=eng,
                     head=[a for a, _ in pairs] if nhwc else None, head_g=[b for _, b in pairs] if nhwc else None,
                     leaves=[q.detach().requires_grad_(True) for q in eng.p],
                     t=torch.zeros(self.capacity, 7, device=dev), valid=torch.zeros(self.capacity, dtype=torch.bool, device=dev),

@@ -31,6 +31,10 @@ View = namedtuple('View', 'buf off C H W cs')
 EvalPlan = namedtuple('EvalPlan', 'shapes buffers x views ops')
 CONV_TYPES = ('convolutional', 'd-convolutional')
 TrainPlan = namedtuple('TrainPlan', 'shapes buffers x act grd forward blocks backward')
+# the non-conv records of TrainPlan.forward: views here, the same types with tensors in TrainEngine.plan (x_g: gradient view of x, or None)
+AddRec = namedtuple('AddRec', 'a b y a_g b_g dy')
+UpRec = namedtuple('UpRec', 'x y x_g dy')
+YoloRec = namedtuple('YoloRec', 'head head_g')
 
 
 class Refused(RuntimeError):
@@ -323,7 +327,7 @@ def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, 
              (ryolo_conv_head_decode_store) -- the conditions of plan_eval's fused head: alone on its input, no BatchNorm, k1 s1, the
              library's own ryolo_conv_head_decode_supported (needs `yolos[i]` = (na, no); whether the block is linear is the engine's
              half: training reads the activation from the modules)
-      add    (a, b, y, a_g, b_g, dy)        up  (x, y, x_g, dy)        yolo  (head, head_g)
+      add    AddRec        up  UpRec        yolo  YoloRec
     blocks: the conv records.  backward: (kind, layer, flags) in launch order (forward reversed); flags say which gradient views the
     entry is the FIRST to write (it overwrites, later ones accumulate): conv (res_g, xin_g), add (a_g, b_g), up x_g; yolo: head index.
 
@@ -441,16 +445,16 @@ def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, 
         elif t == 'shortcut':
             a, b = i - 1, _abs(i, int(d['from']))
             act[i], grd[i] = pair_for(i)
-            forward.append(('add', i, (act[a], act[b], act[i], grd[a], grd[b], grd[i])))
+            forward.append(('add', i, AddRec(act[a], act[b], act[i], grd[a], grd[b], grd[i])))
         elif t == 'upsample':
             act[i], grd[i] = pair_for(i)
-            forward.append(('up', i, (act[i - 1], act[i], grd[i - 1], grd[i])))
+            forward.append(('up', i, UpRec(act[i - 1], act[i], grd[i - 1], grd[i])))
         elif t == 'route':
             if i in alias:
                 act[i], grd[i] = act[alias[i]], grd[alias[i]]
         elif t == 'yolo':
             act[i], grd[i] = act[i - 1], grd[i - 1]
-            forward.append(('yolo', i, (act[i], grd[i])))
+            forward.append(('yolo', i, YoloRec(act[i], grd[i])))
 
     # static accumulate flags of the backward pass (reverse order; the first contribution to a gradient view overwrites it)
     init = set()
@@ -468,15 +472,15 @@ def plan_train(defs, convs, N, H, W, conv0_recompute=True, conv0_one_pass=True, 
         if not need[i + 1 if (kind == 'conv' and i in conv_res) else i]:
             continue                                              # nobody needs a gradient this entry could write
         if kind == 'yolo':
-            first(pl[1])                                          # always the first (sole) writer of the head gradient
+            first(pl.head_g)                                      # always the first (sole) writer of the head gradient
             backward.append((kind, i, heads.index(i)))
         elif kind == 'conv':
             res_first = first(pl['res_g']) if (pl['res_g'] is not None and not pl['res_alias']) else None
             backward.append((kind, i, (res_first, first(pl['xin_g']) if pl['dgrad'] else None)))
         elif kind == 'add':
-            backward.append((kind, i, tuple(first(g) if g is not None else None for g in pl[3:5])))
+            backward.append((kind, i, tuple(first(g) if g is not None else None for g in (pl.a_g, pl.b_g))))
         elif kind == 'up':
-            backward.append((kind, i, first(pl[2]) if pl[2] is not None else None))
+            backward.append((kind, i, first(pl.x_g) if pl.x_g is not None else None))
     return TrainPlan(shp, buffers, x, act, grd, forward, blocks, backward)
 
 

@@ -365,7 +365,7 @@ def test_every_census_class_against_aten(env, cuda_dev):
 
 def test_census_matches_the_engines(env, cuda_dev):
     """the census plans from the cfg text, the engines from the modules (same planner, model/plan.py), pinned at 608^2 / bs 4: every training
-    block's descriptor equals the engine's blk['desc'] field by field, the inference engine's conv launches (layer, kernel name) equal
+    block's descriptor equals the engine's block's desc field by field, the inference engine's conv launches (layer, kernel name) equal
     the census's, and the tensors the engine materialised have the plan's geometry"""
     from rotate_yolov3_amd.cfg import make_cfg
     from rotate_yolov3_amd.model.engine import HipEngine
@@ -377,16 +377,14 @@ def test_census_matches_the_engines(env, cuda_dev):
     te = TrainEngine(m, shape, cuda_dev)
     recs = dc.train_blocks(defs, 608, 608, 4)
     want = {r["layer"]: r for r in recs if r["form"] == "train"}
-    assert sorted(want) == [b["i"] for b in te.blocks]
+    assert sorted(want) == [b.i for b in te.blocks]
     for b in te.blocks:
-        assert dc.desc_tuple(b["desc"]) == dc.desc_tuple(dc.mk_desc(want[b["i"]]["desc"])), (b["i"], dc.desc_tuple(b["desc"]))
-        assert b["recompute"] == want[b["i"]]["recompute"]
-    # (the folded-reduce plan reads the statistics / slopes the first forward sets up)
-    te.forward(torch.rand(shape, generator=torch.Generator().manual_seed(5)).to(cuda_dev))
-    te._plan_reduce_fusion()
+        assert dc.desc_tuple(b.desc) == dc.desc_tuple(dc.mk_desc(want[b.i]["desc"])), (b.i, dc.desc_tuple(b.desc))
+        assert b.recompute == want[b.i]["recompute"]
+    te._plan_reduce_fusion()                                 # (static: needs no forward)
     red = {r["layer"]: r["bnred"] for r in recs if r["form"] == "dgrad"}
-    assert {b["i"]: b.get("red_for") is not None for b in te.blocks if b["xin_g"] is not None} == red
-    assert sorted(r["layer"] for r in recs if r["form"] == "wgrad") == [b["i"] for b in te.blocks if TrainEngine._has_wgrad(b)]
+    assert {b.i: b.red_for is not None for b in te.blocks if b.xin_g is not None} == red
+    assert sorted(r["layer"] for r in recs if r["form"] == "wgrad") == [b.i for b in te.blocks if b.has_wgrad]
     del te
     torch.cuda.empty_cache()
     he = HipEngine(m.eval(), shape, cuda_dev)

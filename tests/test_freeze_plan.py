@@ -277,3 +277,29 @@ def test_a_frozen_plan_keeps_the_views_and_flags_of_what_still_runs(name):
             assert all(f is None or f == g for f, g in zip(flags, fb[(kind, i)]))
         elif kind == "up":
             assert flags is None or flags == fb[(kind, i)]
+
+
+def test_the_records_are_named_and_a_conv_block_has_no_undeclared_state():
+    """AddRec / UpRec / YoloRec are the plain tuples they replaced; a TrainEngine ConvBlock refuses a misspelt attribute"""
+    from rotate_yolov3_amd.model.train_engine import ConvBlock
+    # Darknet-53's shortcuts are all folded into their convs: a second shortcut behind its first unit is a stand-alone add
+    small = DEFS[:5] + [{"type": "shortcut", "from": "-4", "activation": "linear"}]
+    seen = set()
+    for defs, tp in ((small, plan.plan_train(small, dc._convs(small), N, H, W)), (DEFS, _build(None))):
+        for kind, i, pl in tp.forward:
+            if kind == "add":
+                a, b = i - 1, plan._abs(i, int(defs[i]["from"]))
+                assert type(pl) is plan.AddRec and pl == (tp.act[a], tp.act[b], tp.act[i], tp.grd[a], tp.grd[b], tp.grd[i])
+                assert (pl.a, pl.b, pl.y, pl.a_g, pl.b_g, pl.dy) == tuple(pl)
+            elif kind == "up":
+                assert type(pl) is plan.UpRec and pl == (tp.act[i - 1], tp.act[i], tp.grd[i - 1], tp.grd[i])
+                assert (pl.x, pl.y, pl.x_g, pl.dy) == tuple(pl)
+            elif kind == "yolo":
+                assert type(pl) is plan.YoloRec and pl == (tp.act[i], tp.grd[i]) and (pl.head, pl.head_g) == tuple(pl)
+            seen.add(kind)
+    assert seen == {"conv", "add", "up", "yolo"}
+    blk = ConvBlock.__new__(ConvBlock)
+    blk.head_k = 1
+    with pytest.raises(AttributeError):
+        blk.head_kk = 1
+    assert not hasattr(blk, "__dict__")

@@ -63,18 +63,18 @@ class _Checker(object):
         s = {}
         if kind == 'conv':
             res_first, in_first = flags
-            s['dy'] = pl['dy'].clone()
-            if pl['xin_g'] is not None and not in_first:
-                s['xg0'] = pl['xin_g'].clone()
-            if pl['res_g'] is not None and not pl['res_alias'] and not res_first:
-                s['rg0'] = pl['res_g'].clone()
+            s['dy'] = pl.dy.clone()
+            if pl.xin_g is not None and not in_first:
+                s['xg0'] = pl.xin_g.clone()
+            if pl.res_g is not None and not pl.res_alias and not res_first:
+                s['rg0'] = pl.res_g.clone()
         elif kind == 'add':
-            s['dy'] = pl[5].clone()
-            s['a0'] = None if flags[0] else pl[3].clone()
-            s['b0'] = None if flags[1] else pl[4].clone()
+            s['dy'] = pl.dy.clone()
+            s['a0'] = None if flags[0] else pl.a_g.clone()
+            s['b0'] = None if flags[1] else pl.b_g.clone()
         elif kind == 'up':
-            s['dy'] = pl[3].clone()
-            s['x0'] = None if flags else pl[2].clone()
+            s['dy'] = pl.dy.clone()
+            s['x0'] = None if flags else pl.x_g.clone()
         self.snap = s
 
     # ---- after it ran: recompute the block alone from those buffers
@@ -82,8 +82,8 @@ class _Checker(object):
         s = self.snap
         if kind == 'add':
             dy = s['dy'].float()
-            for g, g0, name in ((pl[3], s['a0'], 'a'), (pl[4], s['b0'], 'b')):
-                if g.data_ptr() == pl[5].data_ptr():
+            for g, g0, name in ((pl.a_g, s['a0'], 'a'), (pl.b_g, s['b0'], 'b')):
+                if g.data_ptr() == pl.dy.data_ptr():
                     continue                    # shared buffer (residual chain)
                 ref = dy if g0 is None else g0.float() + dy
                 _close(g, ref, ref.abs() + (0 if g0 is None else g0.float().abs()), "layer %d shortcut pass-through %s" % (i, name))
@@ -96,7 +96,7 @@ class _Checker(object):
             if s['x0'] is not None:
                 ref = ref + s['x0'].float()
                 mag = mag + s['x0'].float().abs()
-            _close(pl[2], ref, mag, "layer %d upsample backward" % i)
+            _close(pl.x_g, ref, mag, "layer %d upsample backward" % i)
             self.checked['up'] += 1
         elif kind == 'conv':
             import os
@@ -106,7 +106,7 @@ class _Checker(object):
                 t0 = time.perf_counter()
                 self._conv(i, pl, flags, s)
                 torch.cuda.synchronize()
-                print("layer %3d  k%d s%d %4d->%4d  %.2f s" % (i, pl['k'], pl['s'], pl['conv'].in_channels, pl['C'], time.perf_counter() - t0), flush=True)
+                print("layer %3d  k%d s%d %4d->%4d  %.2f s" % (i, pl.k, pl.s, pl.conv.in_channels, pl.C, time.perf_counter() - t0), flush=True)
             else:
                 self._conv(i, pl, flags, s)
 
@@ -119,49 +119,49 @@ class _Checker(object):
     def _conv_checked(self, i, b, flags, s):
         eng = self.eng
         res_first, in_first = flags
-        conv, bn = b['conv'], b['bn']
+        conv, bn = b.conv, b.bn
         dy = s['dy'].float()                                    # [n, h, w, c] as the block consumed it
-        c = b['C']
+        c = b.C
         w_b = conv.weight.detach().to(torch.bfloat16).float()   # the packed images are bf16 roundings of the fp32 parameters
-        x = _nchw(b['xin'])[:, :conv.in_channels]
+        x = _nchw(b.xin)[:, :conv.in_channels]
         # fused shortcut: the skip branch receives dy unchanged
-        if b['res_g'] is not None and not b['res_alias']:
+        if b.res_g is not None and not b.res_alias:
             ref = dy if res_first else s['rg0'].float() + dy
-            _close(b['res_g'], ref, ref.abs() + (0 if res_first else s['rg0'].float().abs()), "layer %d fused-shortcut pass-through" % i)
+            _close(b.res_g, ref, ref.abs() + (0 if res_first else s['rg0'].float().abs()), "layer %d fused-shortcut pass-through" % i)
         if bn is not None:
-            mean, invstd, scale, shift = [t[:c].double() for t in b['stats']]
-            if b['z'] is not None:
-                z = b['z'].double()
+            mean, invstd, scale, shift = [t[:c].double() for t in b.stats]
+            if b.z is not None:
+                z = b.z.double()
             else:                                               # layer 0 trains without its conv output: recompute it like the kernel (fp32 accumulate)
-                z = F.conv2d(x, w_b, None, stride=b['s'], padding=b['pad']).permute(0, 2, 3, 1).to(torch.bfloat16).double()     # (csrc/conv0_bwd.hip:166)
+                z = F.conv2d(x, w_b, None, stride=b.s, padding=b.pad).permute(0, 2, 3, 1).to(torch.bfloat16).double()     # (csrc/conv0_bwd.hip:166)
             u = z * scale + shift
             d64 = dy.double()
-            if b['mish']:
+            if b.mish:
                 sp = F.softplus(u)
                 tsp = torch.tanh(sp)
                 g = d64 * (tsp + u * (1 - tsp * tsp) * torch.sigmoid(u))
-            elif b['slope'] is not None:
-                slope = float(b['slope'].detach().reshape(-1)[0])
+            elif b.slope is not None:
+                slope = float(b.slope.detach().reshape(-1)[0])
                 g = torch.where(u > 0, d64, d64 * slope)
             else:
                 g = d64
             xhat = (z - mean) * invstd
             gx = g * xhat
-            m = float(b['npix'])
+            m = float(b.npix)
             s1, s2 = g.sum((0, 1, 2)), gx.sum((0, 1, 2))
             self.pending.append(("layer %d dbeta" % i, bn.bias, s1.float(), 1e-3 * g.abs().sum((0, 1, 2)).float() + 1e-6))
             self.pending.append(("layer %d dgamma" % i, bn.weight, s2.float(), 1e-3 * gx.abs().sum((0, 1, 2)).float() + 1e-6))
-            if isinstance(b['act'], nn.PReLU):
+            if isinstance(b.act, nn.PReLU):
                 t3 = torch.where(u > 0, torch.zeros_like(u), d64 * u)
-                self.pending.append(("layer %d dslope" % i, b['act'].weight, t3.sum().float().reshape(1), 1e-3 * t3.abs().sum().float().reshape(1) + 1e-6))
+                self.pending.append(("layer %d dslope" % i, b.act.weight, t3.sum().float().reshape(1), 1e-3 * t3.abs().sum().float().reshape(1) + 1e-6))
             dz_ref = scale * (g - s1 / m - xhat * (s2 / m))
             mag = (scale.abs() * (g.abs() + (s1 / m).abs() + (xhat * (s2 / m)).abs())).float()
-            if b['dz'] is not None:
-                _close(b['dz'], dz_ref.float(), mag, "layer %d BatchNorm/activation backward dz" % i, extra=1e-5 * float(mag.max()))
-                dz = b['dz'].float()                            # teacher forcing: the convs below consume the ENGINE's dz
+            if b.dz is not None:
+                _close(b.dz, dz_ref.float(), mag, "layer %d BatchNorm/activation backward dz" % i, extra=1e-5 * float(mag.max()))
+                dz = b.dz.float()                            # teacher forcing: the convs below consume the ENGINE's dz
             else:
                 dz = dz_ref.float()                             # layer 0's one-pass backward never materialises dz
-            if b.get('red_part') is not None:
+            if b.red_part is not None:
                 self.checked['bn_reduced'] += 1
         else:
             dz = dy
@@ -169,23 +169,23 @@ class _Checker(object):
                 self.pending.append(("layer %d dbias" % i, conv.bias, dy.sum((0, 1, 2)), 1e-3 * dy.abs().sum((0, 1, 2)) + 1e-6))
         dzc = dz.permute(0, 3, 1, 2).contiguous()
         # weight gradient (fp32 ATen on the bf16 operands the kernel read)
-        dw_ref = torch.nn.grad.conv2d_weight(x, conv.weight.shape, dzc, stride=b['s'], padding=b['pad'])
-        loose = b['dz'] is None                                 # (layer 0: the reference dz is not the bf16-rounded one of a two-pass path)
+        dw_ref = torch.nn.grad.conv2d_weight(x, conv.weight.shape, dzc, stride=b.s, padding=b.pad)
+        loose = b.dz is None                                 # (layer 0: the reference dz is not the bf16-rounded one of a two-pass path)
         self.pending.append(("layer %d dW" % i, conv.weight, dw_ref, None if not loose else "loose"))
         # data gradient into the input's gradient view (first contribution overwrites, later ones accumulate)
-        if b['xin_g'] is not None:
+        if b.xin_g is not None:
             shape = (x.shape[0], conv.in_channels, x.shape[2], x.shape[3])
-            dx = torch.nn.grad.conv2d_input(shape, w_b, dzc, stride=b['s'], padding=b['pad'])
-            absx = torch.nn.grad.conv2d_input(shape, w_b.abs(), dzc.abs(), stride=b['s'], padding=b['pad'])
+            dx = torch.nn.grad.conv2d_input(shape, w_b, dzc, stride=b.s, padding=b.pad)
+            absx = torch.nn.grad.conv2d_input(shape, w_b.abs(), dzc.abs(), stride=b.s, padding=b.pad)
             dx, absx = dx.permute(0, 2, 3, 1), absx.permute(0, 2, 3, 1)
-            got = b['xin_g'][..., :conv.in_channels]
+            got = b.xin_g[..., :conv.in_channels]
             if in_first:
                 _close(got, dx, dx.abs(), "layer %d data gradient (first writer)" % i, extra=1e-4 * absx)
             else:
                 g0 = s['xg0'][..., :conv.in_channels].float()
                 ref = g0 + dx
                 _close(got, ref, ref.abs() + 0.5 * g0.abs(), "layer %d data gradient (accumulating)" % i, extra=1e-4 * absx)
-            if b.get('red_for') is not None:
+            if b.red_for is not None:
                 self.checked['dgrad_bnreduce'] += 1
         self.checked['conv'] += 1
 

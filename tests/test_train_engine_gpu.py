@@ -227,7 +227,7 @@ def test_bn_reduce_folded_into_the_dgrad_at_608_geometry(cuda_dev, monkeypatch):
     monkeypatch.setenv("RYOLO_BN_REDUCE_FUSION", "1")
     runs = [_run(m, x, tg, autocast=True) for _ in range(4)]
     eng = [e for e in m._engines.values() if hasattr(e, "bplan")][0]
-    folded = [pl for kind, i, pl, f in eng.bplan if kind == 'conv' and pl.get('red_for') is not None]
+    folded = [pl for kind, i, pl, f in eng.bplan if kind == 'conv' and pl.red_for is not None]
     assert len(folded) >= 8, len(folded)
     p0, l0, g0 = runs[0]
     for p, l, g in runs[1:]:
@@ -237,7 +237,7 @@ def test_bn_reduce_folded_into_the_dgrad_at_608_geometry(cuda_dev, monkeypatch):
     monkeypatch.setenv("RYOLO_BN_REDUCE_FUSION", "0")
     p1, l1, g1 = _run(m2, x, tg, autocast=True)
     eng2 = [e for e in m2._engines.values() if hasattr(e, "bplan")][0]
-    assert not any(pl.get('red_for') is not None for kind, i, pl, f in eng2.bplan if kind == 'conv')
+    assert not any(pl.red_for is not None for kind, i, pl, f in eng2.bplan if kind == 'conv')
     assert l1 == l0                                             # the forward is untouched
     # the per-channel sums are added in another order (rows per workgroup instead of pixel slabs): dz moves by a bf16 ulp in a few
     # elements, and that noise reaches the parameter gradients in proportion to their conditioning.  Tensors: cosine / norm;
@@ -333,16 +333,16 @@ def test_configs3_bs64_608_step_equals_the_bs4_step_on_a_16_times_repeated_batch
     del ref
     # the batch-dependent dispatch at bs 64: wide tiles on conv_mq, folded BatchNorm reduces, the 128-channel family
     eng = [e for e in m64._engines.values() if hasattr(e, "bplan")][0]
-    folded = [pl for kind, i, pl, f in eng.bplan if kind == 'conv' and pl.get('red_for') is not None]
+    folded = [pl for kind, i, pl, f in eng.bplan if kind == 'conv' and pl.red_for is not None]
     assert len(folded) >= 40, len(folded)
     L = _lib.lib()
     fwd, dgr = {}, {}
     for blk in eng.blocks:
-        d = blk['desc']
-        key = "k%d s%d %d->%d @%d" % (blk['k'], blk['s'], blk['conv'].in_channels, blk['C'], blk['y'].shape[1])
-        fwd[key] = ops.kernel_name_of(L.ryolo_conv_kernel_choice(ctypes.byref(d), 0, 1 if blk['bn'] is not None else 0), blk['k'], blk['s'], d.Cin)
-        if blk['xin_g'] is not None:
-            dgr[key] = ops.kernel_name_of(L.ryolo_conv_dgrad_kernel_choice(ctypes.byref(d), 1 if blk.get('red_for') is not None else 0), blk['k'], 1, d.Cout)
+        d = blk.desc
+        key = "k%d s%d %d->%d @%d" % (blk.k, blk.s, blk.conv.in_channels, blk.C, blk.y.shape[1])
+        fwd[key] = ops.kernel_name_of(L.ryolo_conv_kernel_choice(ctypes.byref(d), 0, 1 if blk.bn is not None else 0), blk.k, blk.s, d.Cin)
+        if blk.xin_g is not None:
+            dgr[key] = ops.kernel_name_of(L.ryolo_conv_dgrad_kernel_choice(ctypes.byref(d), 1 if blk.red_for is not None else 0), blk.k, 1, d.Cout)
     print("bs-64 forward kernels:", sorted(set(fwd.values())))
     print("bs-64 data-gradient kernels:", sorted(set(dgr.values())))
     assert fwd["k3 s1 128->256 @76"] == 'conv_mq<k3,128x256>' and fwd["k3 s1 256->512 @38"] == 'conv_mq<k3,128x256>'
@@ -856,3 +856,48 @@ def test_batched_split_k_reduce_gives_the_bits_of_the_per_layer_reduces(cuda_dev
         assert r[1] == q[1]
         for k in r[2]:
             assert torch.equal(r[2][k], q[2][k]), k
+
+
+@pytest.mark.parametrize("case", ["all_trainable", "stem_weight_frozen", "per_layer_reduce"])
+def test_the_launch_bodies_allocate_nothing_on_their_first_call(cuda_dev, monkeypatch, case):
+    """_forward_launch and _backward_launch are what the hipGraphs capture: everything they need exists after __init__ and
+    _prepare_backward().  torch's allocation counter (with the allocated and reserved bytes) must not move across the FIRST call of
+    each, where a lazy allocation would have nowhere to hide.  Darknet-53 at 64^2, batch 2 (heads 2^2, 4^2, 8^2: the smallest input the
+    engine accepts); a frozen stem weight takes layer 0's two-pass backward with its own workspace, RYOLO_WGRAD_BATCH_REDUCE=0 the
+    shared split-K workspace."""
+    size, bs = 64, 2
+    if case == "per_layer_reduce":
+        monkeypatch.setenv("RYOLO_WGRAD_BATCH_REDUCE", "0")
+    m = _well_conditioned(Darknet(make_cfg.darknet53(size, size), dict(HYP))).to(cuda_dev).train()
+    m.nc, m.arc = 1, "default"
+    if case == "stem_weight_frozen":
+        m.module_list[0].Conv2d.weight.requires_grad_(False)
+    x = torch.rand(bs, 3, size, size, generator=torch.Generator().manual_seed(7)).to(cuda_dev).contiguous()
+    eng = m.train_engine(x.shape, cuda_dev)
+
+    def allocator():
+        return (torch.cuda.memory_stats(cuda_dev).get("allocation.all.allocated"), torch.cuda.memory_allocated(cuda_dev),
+                torch.cuda.memory_reserved(cuda_dev))
+    with torch.cuda.device(cuda_dev), torch.no_grad():
+        eng.x_nhwc.zero_()
+        eng.x_nhwc[..., :3].copy_(x.permute(0, 2, 3, 1))
+        torch.cuda.synchronize(cuda_dev)
+        before = allocator()
+        eng._forward_launch()
+        assert allocator() == before, ("forward", before, allocator())
+        for _, hg in eng.head_pairs:
+            hg.fill_(0.01)
+        segs = eng._prepare_backward()
+        assert eng._prepare_backward() is segs                     # idempotent
+        for lo, hi, _ in segs:
+            before = allocator()
+            eng._backward_launch(lo, hi)
+            assert allocator() == before, ("backward", lo, hi, before, allocator())
+        torch.cuda.synchronize(cuda_dev)
+    b0 = eng.blocks[0]
+    assert before[0] is not None, "torch.cuda.memory_stats has no allocation counter on this build"
+    assert b0.ws0 is not None and b0.one_pass == (case != "stem_weight_frozen") and (b0.dz is None) == b0.one_pass
+    assert (eng._ws_w is not None) == (case == "per_layer_reduce") == (not eng.batch_reduce)
+    assert all((b.ws_w is not None) == (eng.batch_reduce and b.has_wgrad) for b in eng.blocks)
+    g = eng.static_grad[m.module_list[1].Conv2d.weight]
+    assert bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0.0

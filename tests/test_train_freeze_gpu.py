@@ -172,9 +172,9 @@ def test_partial_backward_gives_the_bits_of_the_all_trainable_step(case, pattern
     elif pattern == "H":
         assert ran == [105] and [kind for kind, _, _, _ in eng.bplan] == ["yolo", "conv"]
     elif pattern == "E":
-        assert ran[0] == 42 and [b["i"] for b in eng.blocks if b["wgrad"]] == [42]
+        assert ran[0] == 42 and [b.i for b in eng.blocks if b.wgrad] == [42]
     else:
-        assert ran[0] == 0 and [b["i"] for b in eng.blocks if not b["wgrad"]] == [80]
+        assert ran[0] == 0 and [b.i for b in eng.blocks if not b.wgrad] == [80]
 
 
 @pytest.mark.parametrize("pattern", ["A", "C"])
@@ -198,7 +198,7 @@ def test_frozen_steps_replay_from_graphs_with_the_same_bits(case, pattern):
 
 
 def _count(eng, key):
-    return sum(1 for b in eng.blocks if b.get(key) is not None and not (key == "dz" and b["bn"] is None))
+    return sum(1 for b in eng.blocks if getattr(b, key) is not None and not (key == "dz" and b.bn is None))
 
 
 @pytest.mark.parametrize("pattern", ["A", "B"])
@@ -213,16 +213,16 @@ def test_a_frozen_engine_allocates_nothing_for_entries_that_do_not_run(case, pat
     assert e_all.batch_reduce and eng.batch_reduce
     assert (_count(e_all, "dz"), _count(e_all, "packed_d"), _count(e_all, "ws_w")) == (71, 74, 74)       # (layer 0: one pass, no dz, no dgrad)
     assert _count(eng, "dz") == 0 and _count(eng, "packed_d") == 0
-    assert sorted(b["i"] for b in eng.blocks if b.get("ws_w") is not None) == (list(HEADS) if pattern == "A" else [])
+    assert sorted(b.i for b in eng.blocks if b.ws_w is not None) == (list(HEADS) if pattern == "A" else [])
     assert eng._ws_w is None
     # no gradient view except the three heads'
     grads = set(v for v in eng._tplan.grd if v is not None)
     assert len(grads) == 3 and grads == set(eng._tplan.grd[i] for i in HEADS)
     assert len(set(v for v in e_all._tplan.grd if v is not None)) > 50
     for b in eng.blocks:
-        assert b["xin_g"] is None and b["res_g"] is None and (b["dy"] is not None) == (b["i"] in HEADS)
-        if b["i"] in HEADS:
-            assert b["dz"] is b["dy"]
+        assert b.xin_g is None and b.res_g is None and (b.dy is not None) == (b.i in HEADS)
+        if b.i in HEADS:
+            assert b.dz is b.dy
     assert len(eng._tplan.buffers) < len(e_all._tplan.buffers) - 50
     assert len(eng.static_grad) == (6 if pattern == "A" else 3) and len(e_all.static_grad) == len(case.names)
     assert len(eng.bplan) == 6 and len(e_all.bplan) == 75 + 2 + 3      # convs (their shortcuts folded in), upsamples, yolo layers

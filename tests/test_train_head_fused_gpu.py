@@ -136,11 +136,11 @@ def test_engine_with_fused_heads_equals_the_separate_passes(cuda_dev, monkeypatc
     assert names.count("ryolo_conv_head_decode_store") == 3 and "ryolo_yolo_decode" not in names
     new += [_step(m_new, x, tg) for _ in range(3)]
     e_new = _engine(m_new)
-    heads = [b for b in e_new.blocks if 'head_k' in b]
-    assert len(heads) == 3 and all(b.get('head_fused') for b in heads)
+    heads = [b for b in e_new.blocks if b.head_k is not None]
+    assert len(heads) == 3 and all(b.head_fused for b in heads)
     assert e_new._g_bwd_fold == (True, True, True) and all(gr is not None for gr in e_new.g_bwd) and e_new.g_fwd is not None
     by_id = {id(q): k for k, q in m_new.named_parameters()}
-    bias_names = {by_id[id(b['conv'].bias)]: b['head_k'] for b in heads}
+    bias_names = {by_id[id(b.conv.bias)]: b.head_k for b in heads}
 
     monkeypatch.setenv("RYOLO_HEAD_DECODE", "0")
     monkeypatch.setenv("RYOLO_HEAD_BIAS_FOLD", "0")
@@ -150,7 +150,7 @@ def test_engine_with_fused_heads_equals_the_separate_passes(cuda_dev, monkeypatc
     assert names.count("ryolo_yolo_decode") == 3 and "ryolo_conv_head_decode_store" not in names and "ryolo_head_bias_finalize" not in names
     old += [_step(m_old, x, tg) for _ in range(3)]
     e_old = _engine(m_old)
-    assert not e_old.head_bias_fold and not any(b.get('head_fused') for b in e_old.blocks) and e_old._g_bwd_fold == (False, False, False)
+    assert not e_old.head_bias_fold and not any(b.head_fused for b in e_old.blocks) and e_old._g_bwd_fold == (False, False, False)
     monkeypatch.delenv("RYOLO_HEAD_DECODE")
     monkeypatch.delenv("RYOLO_HEAD_BIAS_FOLD")
     new2 = [_step(m_new2, x, tg) for _ in range(4)]
@@ -198,4 +198,4 @@ def test_engine_takes_two_launches_for_a_576_channel_head(cuda_dev):
     assert names.count("ryolo_yolo_decode") == 3 and "ryolo_conv_head_decode_store" not in names
     assert "ryolo_head_bias_finalize" not in names and names.count("ryolo_bn_act_bwd") >= 3
     eng = _engine(m)
-    assert not any(b.get('head_fused') for b in eng.blocks)
+    assert not any(b.head_fused for b in eng.blocks)

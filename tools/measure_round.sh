@@ -52,8 +52,7 @@ python tools/pw_ablate.py > $out/${tag}_pw_ablation_trace.txt 2>&1
 {
   python tools/step_ab.py --rounds 4 --forward --ab conv_pw=RYOLO_CONV1X1: --ab igemm_1x1=RYOLO_CONV1X1:igemm
   python tools/step_ab.py --rounds 3 --steps 1 --forward --ab fused_heads_and_stem_pair=RYOLO_HEAD_DECODE:1,RYOLO_STEM_PAIR:1 --ab one_launch_per_layer=RYOLO_HEAD_DECODE:0,RYOLO_STEM_PAIR:0 --forward-only
-  # the train step with / without: layer 0's one-pass backward (csrc/conv0_bwd.hip), the BatchNorm reduce folded into the one-tile data gradients
-  python tools/step_ab.py --rounds 4 --ab conv0_one_pass=RYOLO_CONV0_ONE_PASS:1 --ab conv0_two_pass_plus_wgrad=RYOLO_CONV0_ONE_PASS:0
+  # the train step with / without the BatchNorm reduce folded into the one-tile data gradients
   python tools/step_ab.py --rounds 4 --ab bn_reduce_in_tile_dgrads=RYOLO_BN_REDUCE_TILES:1 --ab bn_reduce_separate_pass=RYOLO_BN_REDUCE_TILES:0
   python tools/step_ab.py --rounds 4 --ab stem_dgrads_one_launch=RYOLO_STEM_DGRAD:3 --ab parity_class_launches=RYOLO_STEM_DGRAD:0
   python tools/step_ab.py --rounds 4 --forward --ab layer0_forward_staged_in_lds=RYOLO_CONV0:halo --ab layer0_forward_direct=RYOLO_CONV0:direct
